@@ -21,12 +21,24 @@ Multi-GPU (torch.distributed.run, one rank per GPU), --mode:
     trains the rows train_index[r::world] of the same graph, every rank repeating the same
     full-graph forward/backward, so value = ONE model's edges / time (strong scaling).
 
-At N = 1 the line also carries `sub_configs`: ref (the reference dims), cfg3 (hidden
+A plain run (`--gpus 1 --steps K --warmup W`) builds the workload, warms up, times the K
+steps, writes its outputs if --dump-outputs is given and prints the result line (metric,
+value, unit, higher_is_better, dtype, ms_per_step, config, loss). Everything below that takes
+runs of its own is behind --full: the per-step distribution, the per-group times and
+rooflines, the sub-configs, the drop-in and epoch-with-eval legs, the CPU baseline and, at
+N > 1, the dp leg and the all-reduce's own time.
+
+--dump-outputs DIR: after the timed steps, what the last timed step left for a caller of
+engine.step() (logits, the two losses, the updated parameters) as DIR/<name>.npy. The
+workload and the initial parameters are seeded, so two builds run with the same arguments
+see identical inputs and can be compared output for output.
+
+With --full at N = 1 the line also carries `sub_configs`: ref (the reference dims), cfg3 (hidden
 512, edge-weighted) and cfg5 (RMAT x16, bf16), each timed the same way in a child process
 started before this process touches the GPU (as is the drop-in leg), so that every GEMM
 dispatch of this process belongs to the headline engine's steps.
 
-Beside the engine's number (`value`), rank 0 at N = 1 also reports
+Beside the engine's number (`value`), rank 0 at N = 1 with --full also reports
   * `dropin`: the unmodified reference loop on the dgl shim (plagnn.model + torch Adam,
     exactly what main_normal.py -d cuda runs, code/train.py:197-207);
   * `epoch_with_eval`: the reference-faithful epoch with its per-epoch evaluation
@@ -381,6 +393,29 @@ def _traffic(config, group, calls_per_step):
     return round(b / calls_per_step)
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(engine, outdir: str) -> None:
+    """What the last step left for a caller of engine.step(), as outdir/<name>.npy (float32,
+    the losses float64): the logits of all N rows, the train and val loss, and the updated
+    parameters under their GNN32 names. At most DUMP_BUDGET_BYTES in all: an array larger than
+    its equal share of the budget is cut to a fixed (seed 0) sorted sample of its elements."""
+    arrays = {"logits": engine.logits().detach().float().cpu().numpy(),
+              "loss": np.asarray(engine.losses(), dtype=np.float64)}
+    for k, v in engine.state_dict().items():
+        arrays["param." + k] = v.detach().float().cpu().numpy()
+    cap = DUMP_BUDGET_BYTES // len(arrays)
+    over = sum(a.nbytes for a in arrays.values()) > DUMP_BUDGET_BYTES
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if over and a.nbytes > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+
+
 def _job_of(rank, mode):
     return rank if mode == "replicas" else 0
 
@@ -439,6 +474,8 @@ def run(args, rank, world, dev, dist, mode, breakdown=True):
         dist.barrier()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # before any further step overwrites the last timed one's
+        dump_outputs(engine, args.dump_outputs)
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     edges = torch.tensor([float(engine.edges_per_step)], dtype=torch.float64, device=dev)
     summed = world > 1 and (mode == "replicas" or args.config == "cfg4")
@@ -450,21 +487,23 @@ def run(args, rank, world, dev, dist, mode, breakdown=True):
     value = edges.item() * args.steps / t_max
     # per-step distribution (median of >= 50 steps), after the timed region:
     # each step bracketed by HIP events on the stream the graphs replay on
+    step_dist = None
     n_med = max(50, args.steps)
-    evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_med)]
-    for ea, eb in evs:
-        ea.record()
-        step()
-        eb.record()
-    torch.cuda.synchronize(dev)
-    per_step = np.array(sorted(ea.elapsed_time(eb) for ea, eb in evs))
-    med = float(np.median(per_step))
-    step_dist = {"steps": n_med, "median_ms": round(med, 4),
-                 "p10_ms": round(float(np.percentile(per_step, 10)), 4),
-                 "p90_ms": round(float(np.percentile(per_step, 90)), 4),
-                 "value_at_median": round(edges.item() / (med / 1e3), 1)}
+    if args.full:
+        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(n_med)]
+        for ea, eb in evs:
+            ea.record()
+            step()
+            eb.record()
+        torch.cuda.synchronize(dev)
+        per_step = np.array(sorted(ea.elapsed_time(eb) for ea, eb in evs))
+        med = float(np.median(per_step))
+        step_dist = {"steps": n_med, "median_ms": round(med, 4),
+                     "p10_ms": round(float(np.percentile(per_step, 10)), 4),
+                     "p90_ms": round(float(np.percentile(per_step, 90)), 4),
+                     "value_at_median": round(edges.item() / (med / 1e3), 1)}
     allreduce_ms = None
-    if allreduce is not None and not args.eager:
+    if args.full and allreduce is not None and not args.eager:
         if engine.allreduce_in_graph:
             # the collective is inside the step graph: time the same bucket all-reduces alone,
             # eagerly on the replay stream, as many times (the gradients are rewritten by the
@@ -530,26 +569,17 @@ def run(args, rank, world, dev, dist, mode, breakdown=True):
                          if not summed else "a different graph per rank; value sums the ranks"),
                 "allreduce": ar_info, "loss": {"train": loss_tr, "val": loss_va}}
 
-    # per-group times after the timed region, on rank 0 only (without the collective): each
-    # group's launches of one step captured as a graph and replayed back to back
-    gt = engine.group_times(reps=args.breakdown_reps)
+    group_fields = _group_rooflines(args, engine, bf16) if args.full else {}
     if args.dump_breakdown:  # per launch site, eager steps (diagnostic)
         with open(args.dump_breakdown, "w") as f:
             json.dump(engine.kernel_breakdown(5), f, indent=1)
-    groups, roof = _roofline(engine, gt, bf16)
-    dom = max(groups, key=lambda k: groups[k]["ms"])
-    gemm_name = "gemm_bf16" if bf16 else "gemm_f32"
-    rf = roof(dom)
-    rf["timing"] = ("HIP events around back-to-back replays of a graph holding this group's launches of one step "
-                    "(the step's own buffers), per step")
-    rf["traffic"] = _traffic(args.config, dom, rf.get("launches_per_step"))
     if world > 1:
         par = (f"replicas{world}: independent (round, fold) trainings, no collective" if mode == "replicas" else
                f"dp{world}: shared model, one gradient all-reduce per step, "
                + ("a different perturbation graph per rank" if args.config == "cfg4" else "train rows sharded"))
     else:
         par = "single"
-    return {
+    out = {
         "metric": "edges aggregated/sec per training epoch, full PPI graph",
         "value": round(value, 1),
         "pid": os.getpid(),
@@ -558,7 +588,10 @@ def run(args, rank, world, dev, dist, mode, breakdown=True):
         "steps": args.steps,
         "warmup": args.warmup,
         "ms_per_step": round(t_max / args.steps * 1e3, 4),
-        "step_distribution": step_dist,
+    }
+    if args.full:
+        out["step_distribution"] = step_dist
+    out.update({
         "higher_is_better": True,
         "scaling": "strong" if (world > 1 and not summed) else "weak",
         "vs_baseline": None,
@@ -568,16 +601,33 @@ def run(args, rank, world, dev, dist, mode, breakdown=True):
                    "graph_variant_rank0": wl.variant, "sage_layers": len(dims) - 3, "dims": dims,
                    "edges_per_step": engine.edges_per_step, "mode": mode if world > 1 else "single",
                    "parallelism": par},
+    })
+    if args.full:
+        out.update(group_fields)
+        out["allreduce"] = ar_info
+    out.update({"loss": {"train": loss_tr, "val": loss_va}, "_engine": engine, "_wl": wl})
+    return out
+
+
+def _group_rooflines(args, engine, bf16) -> dict:
+    """The line's per-group fields (--full): per-group times after the timed region, on rank 0
+    only (without the collective), each group's launches of one step captured as a graph and
+    replayed back to back, and the rooflines made from them."""
+    gt = engine.group_times(reps=args.breakdown_reps)
+    groups, roof = _roofline(engine, gt, bf16)
+    dom = max(groups, key=lambda k: groups[k]["ms"])
+    gemm_name = "gemm_bf16" if bf16 else "gemm_f32"
+    rf = roof(dom)
+    rf["timing"] = ("HIP events around back-to-back replays of a graph holding this group's launches of one step "
+                    "(the step's own buffers), per step")
+    rf["traffic"] = _traffic(args.config, dom, rf.get("launches_per_step"))
+    return {
         "roofline": rf,
         "spmm_roofline": {k: roof(k) for k in ("spmm_max_fwd", "spmm_max_bwd") if k in groups},
         # the GEMM group's own roofline when another group dominates (cfg5)
         "gemm_roofline": roof(gemm_name) if gemm_name in groups and gemm_name != dom else None,
         "head_roofline": roof("head") if groups.get("head", {}).get("work") else None,
         "kernels_ms_per_step": {k: round(v["ms"], 4) for k, v in sorted(groups.items(), key=lambda kv: -kv[1]["ms"])},
-        "allreduce": ar_info,
-        "loss": {"train": loss_tr, "val": loss_va},
-        "_engine": engine,
-        "_wl": wl,
     }
 
 
@@ -587,7 +637,7 @@ def _child(args, extra):
     import subprocess
 
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--no-cpu-baseline", "--no-legs", "--sub-configs", "", "--breakdown-reps", str(args.breakdown_reps)] + extra
+           "--full", "--no-cpu-baseline", "--no-legs", "--sub-configs", "", "--breakdown-reps", str(args.breakdown_reps)] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     if r.returncode != 0:
         raise SystemExit(f"child {extra} failed (rc {r.returncode}):\n{r.stderr[-3000:]}")
@@ -655,12 +705,18 @@ def main(argv=None):
     ap.add_argument("--mode", default="auto", choices=["auto", "replicas", "dp"],
                     help="N > 1: replicas = independent (round, fold) trainings, dp = shared model + all-reduce "
                          "(auto: dp for cfg4, replicas otherwise)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: per-step distribution, per-group times and rooflines, sub-configs, "
+                         "drop-in and epoch-with-eval legs, CPU baseline; N > 1: the dp leg and the all-reduce's time")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (logits, losses, parameters) as DIR/<name>.npy")
     ap.add_argument("--sub-configs", default="ref,cfg3,cfg5",
-                    help="N = 1: other configs timed in child processes (comma list, '' for none)")
+                    help="--full, N = 1: other configs timed in child processes (comma list, '' for none)")
     ap.add_argument("--eager", action="store_true", help="no HIP graph (PMC counter passes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-legs", action="store_true", help="skip the drop-in and epoch-with-eval legs")
-    ap.add_argument("--breakdown-reps", type=int, default=5, help="replays of each launch-group timing graph")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-legs", action="store_true", help="--full without the drop-in and epoch-with-eval legs")
+    ap.add_argument("--breakdown-reps", type=int, default=5,
+                    help="--full: replays of each launch-group timing graph")
     ap.add_argument("--dump-breakdown", default="", help="write the per-launch-site breakdown (JSON)")
     ap.add_argument("--dropin-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--chunk-bwd", type=int, default=0, help=argparse.SUPPRESS)  # tuning experiments
@@ -704,9 +760,9 @@ def main(argv=None):
             out["epoch_with_reference_eval"] = dropin_epoch_with_eval(wl, wl.dims, torch.device("cuda"))
         print(json.dumps(out))
         return
-    subs = sub_configs(args) if (world == 1 and args.sub_configs) else None
+    subs = sub_configs(args) if (args.full and world == 1 and args.sub_configs) else None
     dropin = None
-    if world == 1 and not args.no_legs and not W.CONFIGS[args.config][2]:
+    if args.full and world == 1 and not args.no_legs and not W.CONFIGS[args.config][2]:
         try:
             dropin = _child(args, ["--config", args.config, "--dropin-only"])
         except SystemExit as e:  # a leg, not the headline: report it and go on
@@ -737,7 +793,7 @@ def main(argv=None):
     # N > 1: the RCCL data-parallel leg in the same job, after the replicas headline; a leg,
     # so its failure is reported in the line and does not cost the headline
     dp_leg = None
-    if world > 1 and mode == "replicas" and args.mode == "auto":
+    if args.full and world > 1 and mode == "replicas" and args.mode == "auto":
         dp_leg = guarded_dp_leg(args, rank, world, dev, dist, ctrl)
     if out is None:
         _finish(dist)
@@ -748,7 +804,7 @@ def main(argv=None):
     if dp_leg is not None:
         out["dp"] = dp_leg
     legs = {}
-    if world == 1 and not args.no_legs:
+    if args.full and world == 1 and not args.no_legs:
         legs["epoch_with_eval_ms"] = epoch_with_eval_leg(engine, wl, dev)
         if dropin is not None:
             # the engine's forward + backward (every group but Adam; the head includes its
@@ -763,10 +819,11 @@ def main(argv=None):
             if ref_ep:
                 legs["dropin_epoch_with_reference_eval_ms"] = ref_ep["ms"]
     out.update(legs)
-    cpu = None
-    if world == 1 and not args.no_cpu_baseline and not args.config.startswith("cfg5"):
-        cpu = cpu_baseline(wl, wl.dims)
-    out["cpu_baseline"] = cpu
+    if args.full:
+        cpu = None
+        if world == 1 and not args.no_cpu_baseline and not args.config.startswith("cfg5"):
+            cpu = cpu_baseline(wl, wl.dims)
+        out["cpu_baseline"] = cpu
     if subs is not None:
         out["sub_configs"] = subs
     loss = out.pop("loss")

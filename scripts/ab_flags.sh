@@ -2,6 +2,7 @@
 # A/B of bench flag sets on one box: FLAGS="base|--separate-l1-head" (| separated, "base" =
 # none), REPS alternations per config; per-launch-site breakdown of the last one.
 cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out && export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the fields read below are behind bench.py --full
 IFS='|' read -ra FL <<< "${FLAGS:-base}"
 for r in $(seq 1 ${REPS:-2}); do
 for C in ${CONFIGS:-cfg2}; do

@@ -3,6 +3,7 @@
 # the engine line (no legs) for the product build and each variant in LIBS, per config, with
 # the per-launch-site breakdown of the last alternation (gpurun_out/ab6_<cfg>_<lib>.json).
 cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out && export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the fields read below are behind bench.py --full
 if [ -n "${V:-}" ]; then
   PLAGNN_LIB=$PWD/pla-gnn_amd/plagnn/libplagnn_$V.so timeout -k 10 ${TT:-400} python -u -m pytest ${TESTS:-tests/test_gpu_kernels.py} -m gpu -x -q --timeout 200 --timeout-method thread ${KEXPR:+-k "$KEXPR"} > gpurun_out/ab6_tests_$V.log 2>&1
   rc=$?; grep -E "passed|failed|Error|assert" gpurun_out/ab6_tests_$V.log | tail -8; [ $rc -eq 0 ] || exit $rc

@@ -1,6 +1,7 @@
 #!/bin/bash
 # Whole-step bench per library variant: gpurun_out/bab_<v>.json (the shipped library = base).
 cd $GRAFT_REPO_ROOT
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the fields read below are behind bench.py --full
 mkdir -p gpurun_out
 for v in ${LIBS:-base}; do
   if [ "$v" = "base" ]; then unset PLAGNN_LIB; else export PLAGNN_LIB=$GRAFT_REPO_ROOT/pla-gnn_amd/plagnn/libplagnn_$v.so; fi

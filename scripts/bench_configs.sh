@@ -2,6 +2,7 @@
 # One bench.py line per BASELINE config on one GPU (gpurun_out/bench_<cfg>.json); stops at
 # the first failure. CONFIGS / BENCH_ARGS override.
 cd $GRAFT_REPO_ROOT
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the fields read below are behind bench.py --full
 mkdir -p gpurun_out
 for c in ${CONFIGS:-ref cfg3 cfg4 cfg5}; do
   timeout -k 10 500 python bench.py --config $c ${BENCH_ARGS:-} > gpurun_out/bench_$c.json 2> gpurun_out/bench_$c.err

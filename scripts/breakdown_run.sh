@@ -3,6 +3,7 @@
 # builds (LIBS="base v1 ..." -> plagnn/libplagnn[_V].so) and environment settings
 # (ENVS="A=0 A=1", each one run): gpurun_out/bd_<cfg>_<lib>[_<env>].json
 cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out && export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the fields read below are behind bench.py --full
 for C in ${CONFIGS:-cfg2 cfg5}; do
 for V in ${LIBS:-base}; do
 for E in ${ENVS:-NONE=1}; do

@@ -3,6 +3,7 @@
 # default bench line without legs per build, its per-group times (kernels_ms_per_step).
 #   LIBS="base dense" CONFIGS="cfg2 cfg5" bash scripts/engine_ab.sh
 cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out && export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the fields read below are behind bench.py --full
 for C in ${CONFIGS:-cfg2}; do
 for V in ${LIBS:-base}; do
   if [ $V = base ]; then L=$GRAFT_REPO_ROOT/pla-gnn_amd/plagnn/libplagnn.so; else L=$GRAFT_REPO_ROOT/pla-gnn_amd/plagnn/libplagnn_$V.so; fi

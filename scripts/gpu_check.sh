@@ -3,6 +3,7 @@
 # smoke() and the default bench line. Every GPU step has its own limit; the chain stops
 # at the first failure.
 cd $GRAFT_REPO_ROOT
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the fields read below are behind bench.py --full
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 TESTS=${TESTS:-tests}

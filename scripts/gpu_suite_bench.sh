@@ -2,6 +2,7 @@
 # The whole GPU test suite, then the default bench line without the CPU baseline and the
 # sub-configs (the drop-in and epoch-with-eval legs included).
 cd $GRAFT_REPO_ROOT && mkdir -p gpurun_out && export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS:---sub-configs= --no-cpu-baseline}"  # the fields read below are behind bench.py --full
 timeout -k 10 600 python -u -m pytest -x -q --timeout 300 --timeout-method thread -m gpu tests > gpurun_out/pytest_gpu.log 2>&1
 rc=$?; echo "pytest rc=$rc: $(tail -1 gpurun_out/pytest_gpu.log)"
 [ $rc -eq 0 ] || { grep -E "FAILED|Error|error" gpurun_out/pytest_gpu.log | head -20; exit $rc; }

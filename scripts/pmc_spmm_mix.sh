@@ -6,7 +6,7 @@ set -u
 mkdir -p gpurun_out/pmcmix
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
-ARGS="--steps 2 --warmup 2 --no-cpu-baseline --no-legs --breakdown-reps 1"
+ARGS="--full --steps 2 --warmup 2 --no-cpu-baseline --no-legs --breakdown-reps 1"
 run_pass() {
   name=$1; shift
   cd /tmp && timeout -s KILL 120 rocprofv3 --kernel-trace --output-format csv -d $R/gpurun_out/pmcmix/$name -o run --pmc "$@" -- python3 $R/bench.py $ARGS > $R/gpurun_out/pmcmix/$name.out 2> $R/gpurun_out/pmcmix/$name.err

@@ -9,7 +9,7 @@ CONFIG=${CONFIG:-cfg2}
 OUT=$R/gpurun_out/pmc_$CONFIG
 rm -rf $OUT; mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="--config $CONFIG --eager --steps 3 --warmup 2 --no-cpu-baseline --no-legs --sub-configs= --breakdown-reps 1"
+ARGS="--config $CONFIG --eager --full --steps 3 --warmup 2 --no-cpu-baseline --no-legs --sub-configs= --breakdown-reps 1"
 for c in FETCH_SIZE WRITE_SIZE; do
   d=$( [ $c = FETCH_SIZE ] && echo fetch || echo write )
   cd /tmp && timeout -s KILL 240 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $OUT/$d -o %pid% -- python3 $R/bench.py $ARGS > $OUT/$d.out 2> $OUT/$d.err

@@ -2,6 +2,7 @@
 # rocprofv3 kernel-trace summaries of a short bench run per library variant:
 # LIBS="base nolong ..." -> gpurun_out/prof_<v>/  + gpurun_out/prof_ab.txt (by-symbol top kernels)
 cd $GRAFT_REPO_ROOT
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the fields read below are behind bench.py --full
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 for v in ${LIBS:-base}; do

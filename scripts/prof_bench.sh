@@ -4,6 +4,7 @@
 # checks the line's roofline against the profiler (scripts/prof_groups.py).
 #   TAG=r03_cfg2 BENCH_ARGS="" bash scripts/prof_bench.sh
 cd $GRAFT_REPO_ROOT
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the fields read below are behind bench.py --full
 TAG=${TAG:-r03}
 OUT=gpurun_out/prof_$TAG
 rm -rf $OUT; mkdir -p $OUT

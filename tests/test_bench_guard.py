@@ -1,4 +1,4 @@
-"""bench.py at N > 1 (what the driver's 8-GPU SCALE runs): the RCCL dp leg runs after the
+"""bench.py --full at N > 1 (what the driver's 8-GPU SCALE runs): the RCCL dp leg runs after the
 replicas headline in the same processes, and its failure must not cost the headline line.
 Two ranks over gloo on the CPU run bench.main() with the engine replaced by a stand-in
 whose dp leg raises (on every rank, or on rank 1 only); rank 0 must still print the
@@ -45,7 +45,7 @@ def _worker(rank, world, port, outdir, fail_on):
     bench._device = lambda local_rank: torch.device("cpu")
     bench._device_info = lambda dev: {"device": None, "name": "cpu"}
     with open(os.path.join(outdir, f"out{rank}.txt"), "w") as f, contextlib.redirect_stdout(f):
-        bench.main(["--gpus", str(world), "--steps", "2", "--warmup", "1"])
+        bench.main(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--full"])
 
 
 def _free_port():
