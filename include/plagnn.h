@@ -21,6 +21,7 @@
  *   pg_spmm_sum          <- update_all(copy_u / u_mul_e, sum|mean) (SAGEConv 'mean',
  *                           GraphConv, edge_weight=...) and their backward on the
  *                           transposed CSR. Not run by the reference: reference-unpinned.
+ *   pg_sddmm_dot         <- GSpMM.backward's dY for u_mul_e; apply_edges(u_dot_v)
  *   pg_argpos_to_src     <- DGL's argX (source node id of the max) from our compact
  *                           per-row edge positions
  *   pg_sigmoid_multi_loss<- th.sigmoid (code/model.py:29) + multi_loss
@@ -205,6 +206,20 @@ size_t pg_spmm_sum_workspace(const pg_csr_t* g, int64_t F);
 int pg_spmm_sum(const pg_csr_t* g, const float* X, int64_t ldx, int64_t F, int norm_mode,
                 const int32_t* norm_ptr, float* out, int64_t ldo, void* ws, size_t ws_bytes,
                 pg_stream_t stream);
+
+/* Per-edge dot products over the in-CSR g (SDDMM), in slot order:
+ *   de[k] = sum_f D[v,f] * X[col[k],f]                 for every slot k of row v
+ *   norm_mode 1: the finished sum is divided by (float)(entry count of row v)  (mean)
+ *   argpos != NULL (max form): only the f with argpos[v,f] == k - ptr[v] are summed
+ *     (arg_kind PG_ARG_U16 | PG_ARG_I32, PG_ARG_DEAD_NONE accepted: "none" matches no edge)
+ * g->ew is not read. Every de[k], k < nnz, is written exactly once (no workspace, no
+ * atomics: each slot lies in exactly one schedule item), in a fixed summation order, so
+ * the result is bitwise reproducible. The vector path is taken when F, ldd, ldx (and lda
+ * in the max form) are multiples of 4 and D, X (and argpos) are 16-byte aligned. The call
+ * allocates nothing and does not synchronise (graph-capturable). */
+int pg_sddmm_dot(const pg_csr_t* g, const float* D, int64_t ldd, const float* X, int64_t ldx,
+                 int64_t F, int norm_mode, const void* argpos, int64_t lda, int arg_kind,
+                 float* de, pg_stream_t stream);
 
 /* argx[v,f] = col[ptr[v] + argpos[v,f]] (DGL's argX, int64), -1 where none. */
 int pg_argpos_to_src(const pg_csr_t* g, const void* argpos, int64_t lda, int arg_kind,
@@ -470,6 +485,10 @@ int pg_spmm_sum_cpu(const pg_csr_t* g, const float* X, int64_t ldx, int64_t F, i
                     const int32_t* norm_ptr, float* out, int64_t ldo);
 int pg_argpos_to_src_cpu(const pg_csr_t* g, const void* argpos, int64_t lda, int arg_kind,
                          int64_t F, int64_t* argx, int64_t ldx);
+/* f32 accumulation in ascending f, OpenMP over rows; needs no work schedule. */
+int pg_sddmm_dot_cpu(const pg_csr_t* g, const float* D, int64_t ldd, const float* X, int64_t ldx,
+                     int64_t F, int norm_mode, const void* argpos, int64_t lda, int arg_kind,
+                     float* de);
 
 /* ---------------- device: §8f — edge clustering coefficient ---------------- */
 
@@ -548,7 +567,8 @@ int pg_version(void); /* 2: pg_csr_t.einv; 3: pg_spmm_max_bwd fwd_out; 5: no in-
                          9: pg_gemm_f32_group; 10: the in-CSR's epos = transposed
                          indices (transposed max-backward descriptors), pg_gemm_f32_cat;
                          11: pg_pad2d_group; 12: pg_mlp_l1_head;
-                         13: pg_mlp_l1_split, pg_mlp_l1_head_ex, pg_adam_apply_l1 */
+                         13: pg_mlp_l1_split, pg_mlp_l1_head_ex, pg_adam_apply_l1;
+                         13 also: pg_sddmm_dot */
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,20 @@ inline int check_csr(const pg_csr_t* g, const char* who, bool need_sched) {
   return PG_OK;
 }
 
+// pg_sddmm_dot[_cpu]: the checks both entry points share (argpos NULL: arg_kind is not read)
+inline int check_sddmm(const pg_csr_t* g, const char* who, int64_t ldd, int64_t ldx, int64_t F,
+                       int norm_mode, const void* argpos, int64_t lda, int arg_kind) {
+  if (F < 0 || ldd < F || ldx < F || (argpos && lda < F))
+    return set_error(PG_ERR_INVALID, "%s: bad F/leading dims", who);
+  if (norm_mode < 0 || norm_mode > 1)
+    return set_error(PG_ERR_INVALID, "%s: bad norm_mode %d", who, norm_mode);
+  if (argpos && !valid_arg_kind(arg_kind & ~PG_ARG_DEAD_NONE))
+    return set_error(PG_ERR_INVALID, "%s: bad arg_kind %d", who, arg_kind);
+  if (argpos && (arg_kind & ~PG_ARG_DEAD_NONE) == PG_ARG_U16 && g->max_deg >= 0xFFFF)
+    return set_error(PG_ERR_INVALID, "%s: degree too large for u16 records", who);
+  return PG_OK;
+}
+
 }  // namespace pg
 
 #define PG_TRY(expr)            \

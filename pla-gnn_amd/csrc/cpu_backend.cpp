@@ -7,6 +7,7 @@
 // SpMMCmpCsr CPU loop.
 #include <cmath>
 #include <limits>
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -78,6 +79,31 @@ void max_bwd(const pg_csr_t* g, const pg_csr_t* gt, const A* arg, int64_t lda, c
       const float* m = mask + u * ldm;
       for (int64_t f = 0; f < F; ++f)
         if (!(m[f] > 0.f)) d[f] = 0.f;
+    }
+  }
+}
+
+// A = void: the plain form (no records read)
+template <typename A>
+void sddmm_dot(const pg_csr_t* g, const float* D, int64_t ldd, const float* X, int64_t ldx,
+               int64_t F, bool mean, const A* arg, int64_t lda, float* de) {
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t v = 0; v < g->n_rows; ++v) {
+    const int32_t b = g->ptr[v], e = g->ptr[v + 1];
+    const float* d = D + v * ldd;
+    const float deg = (float)(e - b);
+    for (int32_t k = b; k < e; ++k) {
+      const float* x = X + (int64_t)g->col[k] * ldx;
+      float acc = 0.f;
+      if constexpr (std::is_void<A>::value) {
+        for (int64_t f = 0; f < F; ++f) acc += d[f] * x[f];
+      } else {
+        const A* a = arg + v * lda;
+        const A pos = (A)(k - b);  // never the "none" value: k - b < max_deg
+        for (int64_t f = 0; f < F; ++f)
+          if (a[f] == pos) acc += d[f] * x[f];
+      }
+      de[k] = mean ? acc / deg : acc;
     }
   }
 }
@@ -167,6 +193,23 @@ int pg_argpos_to_src_cpu(const pg_csr_t* g, const void* argpos, int64_t lda, int
       argx[v * ldx + f] = p < 0 ? -1 : (int64_t)g->col[g->ptr[v] + p];
     }
   }
+  return pg::ok();
+}
+
+int pg_sddmm_dot_cpu(const pg_csr_t* g, const float* D, int64_t ldd, const float* X, int64_t ldx,
+                     int64_t F, int norm_mode, const void* argpos, int64_t lda, int arg_kind,
+                     float* de) {
+  PG_TRY(pg::check_csr(g, "pg_sddmm_dot_cpu", false));
+  PG_TRY(pg::check_sddmm(g, "pg_sddmm_dot_cpu", ldd, ldx, F, norm_mode, argpos, lda, arg_kind));
+  if (g->nnz == 0 || g->n_rows == 0) return pg::ok();
+  if (!de || (F > 0 && (!D || !X))) return pg::set_error(PG_ERR_INVALID, "pg_sddmm_dot_cpu: NULL buffer");
+  const bool mean = norm_mode == 1;
+  if (!argpos)
+    sddmm_dot<void>(g, D, ldd, X, ldx, F, mean, nullptr, 0, de);
+  else if ((arg_kind & ~PG_ARG_DEAD_NONE) == PG_ARG_U16)
+    sddmm_dot<uint16_t>(g, D, ldd, X, ldx, F, mean, (const uint16_t*)argpos, lda, de);
+  else
+    sddmm_dot<int32_t>(g, D, ldd, X, ldx, F, mean, (const int32_t*)argpos, lda, de);
   return pg::ok();
 }
 

@@ -12,7 +12,9 @@ The reference touches exactly this surface:
   from dgl.nn.pytorch import SAGEConv                code/model.py:7
   SAGEConv(in, out, 'pool')(g, h)                    code/model.py:13-15, 20-24
 plus ``update_all`` with ``dgl.function`` builtins (copy_u / u_mul_e with sum / mean /
-max), which SAGEConv itself is defined by.
+max), which SAGEConv itself is defined by, and ``apply_edges`` with ``u_dot_v`` (DGL's
+SDDMM). Edge weights may require grad: every weighted aggregation is differentiable with
+respect to them, as DGL's GSpMM.backward is.
 
 Message passing on a CUDA (HIP) device always runs in libplagnn.so; a missing library is
 an error, never a silent fallback.
@@ -224,6 +226,8 @@ class DGLGraph:
 
         if not isinstance(message_func, _Message) or not isinstance(reduce_func, _Reduce):
             raise NotImplementedError("update_all supports dgl.function builtins only")
+        if message_func.op not in ("copy_u", "u_mul_e"):
+            raise NotImplementedError(f"update_all: message function {message_func.op} is not supported")
         if reduce_func.msg != message_func.out:
             raise ValueError("reduce function reads a message the message function does not write")
         X = self.ndata[message_func.lhs]
@@ -247,6 +251,24 @@ class DGLGraph:
         self.ndata[reduce_func.out] = out
         if apply_node_func is not None:
             self.ndata.update(apply_node_func(_NodeBatch(self)))
+
+    def apply_edges(self, func, edges=None, etype=None):
+        """apply_edges(dgl.function.u_dot_v(lhs, rhs, out)): edata[out][e] = the dot product of
+        ndata[lhs][src_e] and ndata[rhs][dst_e], shape (E, 1), in edge-id order (DGL's SDDMM,
+        the engine's pg_sddmm_dot)."""
+        from .function import _Message
+
+        if not isinstance(func, _Message) or func.op != "u_dot_v" or edges is not None:
+            raise NotImplementedError("apply_edges supports dgl.function.u_dot_v on all edges only")
+        lhs, rhs = self.ndata[func.lhs], self.ndata[func.rhs]
+        if lhs.shape != rhs.shape:
+            raise ValueError(f"u_dot_v: operand shapes {tuple(lhs.shape)} and {tuple(rhs.shape)} differ")
+        dg = self._device_graph(lhs.device)
+        n = lhs.shape[0]
+        de = _engine().ops.EdgeDot.apply(lhs.reshape(n, -1).float(), rhs.reshape(n, -1).float(), dg)
+        # slot order -> edge-id order: eid is a permutation, so every element is written once
+        out = torch.empty_like(de).index_copy(0, dg.eid, de)
+        self.edata[func.out] = out.to(lhs.dtype).reshape(-1, 1)
 
     def __repr__(self):
         return (f"Graph(num_nodes={self._n}, num_edges={self.num_edges()},\n"

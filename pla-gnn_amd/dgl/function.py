@@ -1,5 +1,6 @@
 """dgl.function builtins understood by DGLGraph.update_all (the forms SAGEConv uses:
-copy_u('h', 'm') / u_mul_e('h', '_edge_weight', 'm') with sum / mean / max)."""
+copy_u('h', 'm') / u_mul_e('h', '_edge_weight', 'm') with sum / mean / max) and by
+DGLGraph.apply_edges (u_dot_v('a', 'b', 'out'), DGL's SDDMM)."""
 from __future__ import annotations
 
 
@@ -22,6 +23,11 @@ copy_src = copy_u  # DGL < 0.8 name
 
 def u_mul_e(lhs_field: str, rhs_field: str, out: str) -> _Message:
     return _Message("u_mul_e", lhs_field, rhs_field, out)
+
+
+def u_dot_v(lhs_field: str, rhs_field: str, out: str) -> _Message:
+    """out[e] = <ndata[lhs][src_e], ndata[rhs][dst_e]>, shape (E, 1) (apply_edges only)."""
+    return _Message("u_dot_v", lhs_field, rhs_field, out)
 
 
 def sum(msg: str, out: str) -> _Reduce:  # noqa: A001  (DGL's name)

@@ -147,6 +147,7 @@ SIGNATURES = {
     "pg_spmm_max_bwd_scatter": (_i, [_csr, _vp, _i64, _i, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
     "pg_spmm_sum_workspace": (_sz, [_csr, _i64]),
     "pg_spmm_sum": (_i, [_csr, _vp, _i64, _i64, _i, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "pg_sddmm_dot": (_i, [_csr, _vp, _i64, _vp, _i64, _i64, _i, _vp, _i64, _i, _vp, _vp]),
     "pg_argpos_to_src": (_i, [_csr, _vp, _i64, _i, _i64, _vp, _i64, _vp]),
     "pg_bias_act": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _f, _vp]),
     "pg_act_bwd": (_i, [_vp, _i64, _vp, _i64, _i64, _i64, _i, _f, _vp]),
@@ -200,6 +201,7 @@ SIGNATURES = {
     "pg_spmm_max_bwd_cpu": (_i, [_csr, _csr, _vp, _i64, _i, _vp, _i64, _i64, _vp, _i64, _vp, _i64]),
     "pg_spmm_sum_cpu": (_i, [_csr, _vp, _i64, _i64, _i, _vp, _vp, _i64]),
     "pg_argpos_to_src_cpu": (_i, [_csr, _vp, _i64, _i, _i64, _vp, _i64]),
+    "pg_sddmm_dot_cpu": (_i, [_csr, _vp, _i64, _vp, _i64, _i64, _i, _vp, _i64, _i, _vp]),
     "pg_last_error_string": (ctypes.c_char_p, []),
     "pg_version": (_i, []),
 }

@@ -11,6 +11,7 @@ import weakref
 from typing import Optional, Tuple
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._lib import call, ptr
@@ -164,6 +165,31 @@ def spmm_sum(dg: DeviceGraph, X: torch.Tensor, mean: bool = False,
     else:
         call("pg_spmm_sum_cpu", g, ptr(X), _ld(X), F, norm_mode, ptr(norm_ptr), ptr(out), _ld(out))
     return out
+
+
+def sddmm_dot(dg: DeviceGraph, D: torch.Tensor, X: torch.Tensor, mean: bool = False,
+              argpos: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-edge dot products de[k] = sum_f D[dst_k, f] * X[src_k, f] in in-CSR slot order
+    (pg_sddmm_dot): the gradient of a sum (`mean`: mean) aggregation w.r.t. its u_mul_e
+    weights, with D = dout. With `argpos` (a max aggregation's records, plain or dead-none)
+    only the features edge k won are summed: the max aggregation's weight gradient."""
+    _check_device(dg, D, X, argpos)
+    if D.dtype != torch.float32 or X.dtype != torch.float32:
+        raise TypeError("sddmm_dot: float32 operands expected")
+    n, F = dg.num_nodes, D.shape[1]
+    if D.shape[0] != n or tuple(X.shape) != (n, F):
+        raise ValueError(f"sddmm_dot: operands {tuple(D.shape)}, {tuple(X.shape)} on a graph of {n} nodes")
+    if argpos is not None and (argpos.dtype != dg.arg_dtype or tuple(argpos.shape) != (n, F)):
+        raise ValueError("sddmm_dot: argpos does not match the graph's record type or the operands' shape")
+    de = torch.empty(dg.num_edges, dtype=torch.float32, device=D.device)
+    g = dg.fwd.struct(None)
+    lda = _ld(argpos) if argpos is not None else 0
+    args = (g, ptr(D), _ld(D), ptr(X), _ld(X), F, int(mean), ptr(argpos), lda, dg.arg_kind, ptr(de))
+    if dg.is_cuda:
+        call("pg_sddmm_dot", *args, _stream(D))
+    else:
+        call("pg_sddmm_dot_cpu", *args)
+    return de
 
 
 def argpos_to_src(dg: DeviceGraph, argpos: torch.Tensor) -> torch.Tensor:
@@ -378,40 +404,70 @@ def col_sum(x: torch.Tensor, out: Optional[torch.Tensor] = None, accumulate: boo
 
 # ------------------------------------------------------------------ autograd
 class MaxAggregate(torch.autograd.Function):
-    """update_all(copy_u('h','m') | u_mul_e, max('m','neigh')) with the DGL backward."""
+    """update_all(copy_u('h','m') | u_mul_e, max('m','neigh')) with the DGL backward; the
+    weights' gradient (u_mul_e) is the per-edge product over the features the edge won."""
 
     @staticmethod
     def forward(ctx, X, dg, ew_slots):
-        if ew_slots is not None and ew_slots.requires_grad:
-            raise NotImplementedError("gradient w.r.t. edge weights of a max aggregation")
-        out, argpos = spmm_max(dg, X.contiguous(), ew_slots)
+        X = X.contiguous()
+        out, argpos = spmm_max(dg, X, ew_slots)
         ctx.dg = dg
-        ctx.save_for_backward(argpos, ew_slots)
+        ctx.need_ew = ew_slots is not None and ctx.needs_input_grad[2]
+        ctx.save_for_backward(argpos, ew_slots, X if ctx.need_ew else None)
         return out
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dout):
-        argpos, ew_slots = ctx.saved_tensors
-        dx = spmm_max_backward(ctx.dg, argpos, dout.contiguous(), ew_slots)
-        return dx, None, None
+        argpos, ew_slots, X = ctx.saved_tensors
+        dout = dout.contiguous()
+        dx = spmm_max_backward(ctx.dg, argpos, dout, ew_slots) if ctx.needs_input_grad[0] else None
+        d_ew = sddmm_dot(ctx.dg, dout, X, argpos=argpos) if ctx.need_ew else None
+        return dx, None, d_ew
 
 
 class SumAggregate(torch.autograd.Function):
-    """update_all(copy_u | u_mul_e, sum | mean); backward on the transposed CSR."""
+    """update_all(copy_u | u_mul_e, sum | mean); backward on the transposed CSR, the
+    weights' gradient (u_mul_e) as per-edge dot products of dout and X."""
 
     @staticmethod
     def forward(ctx, X, dg, ew_slots, mean):
-        if ew_slots is not None and ew_slots.requires_grad:
-            raise NotImplementedError("gradient w.r.t. edge weights of a sum aggregation")
+        X = X.contiguous()
         ctx.dg, ctx.mean = dg, mean
-        ctx.save_for_backward(ew_slots)
-        return spmm_sum(dg, X.contiguous(), mean, ew_slots)
+        ctx.need_ew = ew_slots is not None and ctx.needs_input_grad[2]
+        ctx.save_for_backward(ew_slots, X if ctx.need_ew else None)
+        return spmm_sum(dg, X, mean, ew_slots)
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dout):
-        (ew_slots,) = ctx.saved_tensors
-        dx = spmm_sum(ctx.dg, dout.contiguous(), ctx.mean, ew_slots, transpose=True)
-        return dx, None, None, None
+        ew_slots, X = ctx.saved_tensors
+        dout = dout.contiguous()
+        dx = spmm_sum(ctx.dg, dout, ctx.mean, ew_slots, transpose=True) if ctx.needs_input_grad[0] else None
+        d_ew = sddmm_dot(ctx.dg, dout, X, mean=ctx.mean) if ctx.need_ew else None
+        return dx, None, d_ew, None
+
+
+class EdgeDot(torch.autograd.Function):
+    """apply_edges(u_dot_v(lhs, rhs, out)): de[k] = sum_f lhs[src_k, f] * rhs[dst_k, f] in
+    in-CSR slot order (pg_sddmm_dot); the input gradients are weighted sum aggregations
+    with the incoming edge gradient as the weights."""
+
+    @staticmethod
+    def forward(ctx, lhs, rhs, dg):
+        lhs, rhs = lhs.contiguous(), rhs.contiguous()
+        ctx.dg = dg
+        ctx.save_for_backward(lhs, rhs)
+        return sddmm_dot(dg, rhs, lhs)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, de):
+        lhs, rhs = ctx.saved_tensors
+        de = de.contiguous()
+        d_lhs = spmm_sum(ctx.dg, rhs, ew_slots=de, transpose=True) if ctx.needs_input_grad[0] else None
+        d_rhs = spmm_sum(ctx.dg, lhs, ew_slots=de) if ctx.needs_input_grad[1] else None
+        return d_lhs, d_rhs, None
 
 
 def _padded(n: int, F: int, device) -> torch.Tensor:
@@ -478,13 +534,20 @@ class SagePool(torch.autograd.Function):
     K = 2F product [H | M] [Wself | Wneigh]^T, dead-none max records (the backward reads no
     relu' mask), the weight gradients of fc_self and fc_neigh as one product dY^T [H | M],
     and the input gradient as one stacked product [dY | dP] [Wself ; Wpool]. On the CPU
-    device: the plain composition (DGL's CPU backend role)."""
+    device: the plain composition (DGL's CPU backend role).
+
+    Edge weights that require grad get their gradient from sddmm_dot's max form (dM and P
+    over the argmax records); the HIP paths then record plain argmax and apply the relu'
+    mask from P. With frozen weights every path makes the calls described above."""
 
     @staticmethod
     def forward(ctx, h, w_pool, b_pool, w_self, w_neigh, bias, dg, ew_slots):
         h = h.contiguous()
         ctx.dg = dg
         ctx.has_bias = bias is not None
+        # a weight gradient needs plain argmax records: a dead-none record drops the entries
+        # whose maximum is 0, and an edge with w = 0, P > 0 there has d/dw = dM * P != 0
+        ctx.need_ew = ew_slots is not None and ctx.needs_input_grad[7]
         if h.device.type == "cuda":
             return SagePool._forward_gpu(ctx, h, w_pool, b_pool, w_self, w_neigh, bias, dg, ew_slots)
         N, Fin = h.shape
@@ -510,7 +573,7 @@ class SagePool(torch.autograd.Function):
                 return out
         ctx.cat = False
         fpad = Fp - Fin
-        keep = torch.is_grad_enabled() and any(ctx.needs_input_grad[:6])
+        keep = torch.is_grad_enabled() and (any(ctx.needs_input_grad[:6]) or ctx.need_ew)
         HM, ctx.hm_key = _hm_buffer(h, Fp, keep)
         # the padded weight images in one launch (pg_pad2d_group)
         Fo = w_self.shape[0]
@@ -522,7 +585,7 @@ class SagePool(torch.autograd.Function):
         P = torch.empty(N, Fp, dtype=torch.float32, device=h.device)
         gemm(HM[:, :Fp], Wpool, transb=True, out=P, bias=bpool, act=_lib.PG_ACT_RELU)
         argpos = torch.empty(N, Fp, dtype=dg.arg_dtype, device=h.device)
-        spmm_max(dg, P, ew_slots, out=HM[:, Fp:], argpos=argpos, dead_none=True)
+        spmm_max(dg, P, ew_slots, out=HM[:, Fp:], argpos=argpos, dead_none=not ctx.need_ew)
         Y = gemm(HM, Wcat, transb=True, bias=bias)
         ctx.gpu = True
         ctx.save_for_backward(HM, P, argpos, Wpool, Wcat, ew_slots)
@@ -543,7 +606,7 @@ class SagePool(torch.autograd.Function):
         gemm(h, w_pool, transb=True, out=P, bias=b_pool.contiguous(), act=_lib.PG_ACT_RELU)
         M = torch.empty(N, Fin, dtype=torch.float32, device=h.device)
         argpos = torch.empty(N, Fin, dtype=dg.arg_dtype, device=h.device)
-        spmm_max(dg, P, ew_slots, out=M, argpos=argpos, dead_none=True)
+        spmm_max(dg, P, ew_slots, out=M, argpos=argpos, dead_none=not ctx.need_ew)
         Y = gemm_cat(h, M, w_self, w_neigh, transb=True, bias=bias)
         if Y is None:
             Y = gemm(torch.cat([h, M], 1), torch.cat([w_self, w_neigh], 1), transb=True, bias=bias)
@@ -572,7 +635,8 @@ class SagePool(torch.autograd.Function):
             d_b = col_sum(dY)
         dM = gemm(dY, w_neigh)
         dP = torch.empty(N, Fin, dtype=torch.float32, device=dY.device)
-        spmm_max_backward(dg, argpos, dM, ew_slots, mask=P, dx=dP, dead_none=True)
+        spmm_max_backward(dg, argpos, dM, ew_slots, mask=P, dx=dP, dead_none=not ctx.need_ew)
+        d_ew = sddmm_dot(dg, dM, P, argpos=argpos) if ctx.need_ew else None
         d_bp = torch.empty(Fin, dtype=torch.float32, device=dY.device) if need_bp else None
         d_wp = None
         if need_wp:
@@ -586,9 +650,10 @@ class SagePool(torch.autograd.Function):
             d_h = gemm_cat(dY, dP, w_self, w_pool)
             if d_h is None:
                 d_h = gemm(torch.cat([dY, dP], 1), torch.cat([w_self, w_pool], 0))
-        return d_h, d_wp, d_bp, d_ws, d_wn, d_b, None, None
+        return d_h, d_wp, d_bp, d_ws, d_wn, d_b, None, d_ew
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dY):
         if ctx.gpu and ctx.cat:
             return SagePool._backward_gpu_cat(ctx, dY)
@@ -609,6 +674,7 @@ class SagePool(torch.autograd.Function):
         gemm(dY, w_neigh, out=dMb[:, :Fin])
         dPb = torch.empty_like(Pb)
         spmm_max_backward(dg, argpos, dMb, ew_slots, mask=Pb, dx=dPb)
+        d_ew = sddmm_dot(dg, dMb, Pb, argpos=argpos) if ctx.need_ew else None
         dP = dPb[:, :Fin]
         d_bp = torch.empty(Fin, dtype=torch.float32, device=dY.device) if need_bp else None
         d_wp = gemm(dP, h, transa=True, rowsum=d_bp) if need_wp else None
@@ -618,7 +684,7 @@ class SagePool(torch.autograd.Function):
         if need_h:
             d_h = gemm(dY, w_self)
             gemm(dP, w_pool, out=d_h, beta=1.0)
-        return d_h, d_wp, d_bp, d_ws, d_wn, d_b, None, None
+        return d_h, d_wp, d_bp, d_ws, d_wn, d_b, None, d_ew
 
     @staticmethod
     def _backward_gpu(ctx, dY):
@@ -653,9 +719,11 @@ class SagePool(torch.autograd.Function):
         elif d_b is not None:
             d_b = col_sum(dY)
         dM = gemm(dY, Wcat[:, Fp:])
-        # dead-none records: the relu' mask of P is implied (P is not read)
+        # dead-none records: the relu' mask of P is implied (P is not read); plain records
+        # (a weight gradient is wanted): the mask is applied from P
         dP = DYP[:, Fo:] if DYP is not None else torch.empty(N, Fp, dtype=torch.float32, device=dY.device)
-        spmm_max_backward(dg, argpos, dM, ew_slots, mask=P, dx=dP, dead_none=True)
+        spmm_max_backward(dg, argpos, dM, ew_slots, mask=P, dx=dP, dead_none=not ctx.need_ew)
+        d_ew = sddmm_dot(dg, dM, P, argpos=argpos) if ctx.need_ew else None
         d_bp_p = torch.empty(Fp, dtype=torch.float32, device=dY.device) if need_bp else None
         d_wp = d_bp = None
         if need_wp:
@@ -671,4 +739,4 @@ class SagePool(torch.autograd.Function):
         if need_h:  # one stacked product [dY | dP] [Wself ; Wpool]
             Wstack = torch.cat([Wcat[:, :Fp], Wpool], 0)
             d_h = gemm(DYP, Wstack)[:, :Fin]
-        return d_h, d_wp, d_bp, d_ws, d_wn, d_b, None, None
+        return d_h, d_wp, d_bp, d_ws, d_wn, d_b, None, d_ew
