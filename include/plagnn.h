@@ -22,6 +22,11 @@
  *                           GraphConv, edge_weight=...) and their backward on the
  *                           transposed CSR. Not run by the reference: reference-unpinned.
  *   pg_sddmm_dot         <- GSpMM.backward's dY for u_mul_e; apply_edges(u_dot_v)
+ *   pg_edge_softmax_*    <- dgl.ops.edge_softmax (norm_by='dst') forward and backward, H heads
+ *   pg_spmm_sum_heads    <- update_all(u_mul_e, sum) with (N, H, Fh) features and (E, H, 1)
+ *                           weights (GATConv's aggregation) and its feature gradient
+ *   pg_sddmm_dot_heads   <- its weight gradient; apply_edges(u_dot_v) on (N, H, Fh) operands.
+ *                           Attention is not used by the reference: reference-unpinned.
  *   pg_argpos_to_src     <- DGL's argX (source node id of the max) from our compact
  *                           per-row edge positions
  *   pg_sigmoid_multi_loss<- th.sigmoid (code/model.py:29) + multi_loss
@@ -220,6 +225,37 @@ int pg_spmm_sum(const pg_csr_t* g, const float* X, int64_t ldx, int64_t F, int n
 int pg_sddmm_dot(const pg_csr_t* g, const float* D, int64_t ldd, const float* X, int64_t ldx,
                  int64_t F, int norm_mode, const void* argpos, int64_t lda, int arg_kind,
                  float* de, pg_stream_t stream);
+
+/* Multi-head attention over the in-CSR g (dgl.ops.edge_softmax and GATConv's aggregation):
+ * edge features are [nnz][ld] row-major in in-CSR SLOT order with H heads, ld >= H; v is the
+ * row (destination) that owns slot k. 1 <= H <= 64, Fh >= 1, H * Fh as wide as pg_spmm_sum
+ * takes; outputs must not alias inputs. nnz == 0 and n_rows == 0 succeed (pg_spmm_sum_heads
+ * still zero-fills the rows of a graph without edges). Every output element is written
+ * exactly once, without atomics, in a reduction order that depends on the graph and the
+ * shapes only: two runs give bitwise-equal results. Nothing is allocated or synchronised.
+ *
+ * a[k,h] = exp(s[k,h] - m[v,h]) / sum_{k' in row v} exp(s[k',h] - m[v,h]),
+ * m[v,h] = max_{k' in row v} s[k',h]. A -inf score gives a = 0 when its row has a finite
+ * score for that head; a row whose scores for a head are all -inf or contain NaN is
+ * unspecified. One wave per row, one workgroup per row the schedule splits. */
+int pg_edge_softmax_fwd(const pg_csr_t* g, const float* s, int64_t lds, int32_t H, float* a,
+                        int64_t lda, pg_stream_t stream);
+/* ds[k,h] = a[k,h] * (da[k,h] - sum_{k' in row v} a[k',h] * da[k',h]) */
+int pg_edge_softmax_bwd(const pg_csr_t* g, const float* a, int64_t lda, const float* da,
+                        int64_t ldda, int32_t H, float* ds, int64_t ldds, pg_stream_t stream);
+/* out[r, h*Fh + j] = sum_{k in row r} A[(eslot ? eslot[k] : k), h] * X[col[k], h*Fh + j];
+ * rows without entries: 0. g->ew is not read. On the transposed CSR (eslot set) this is the
+ * feature gradient. The vector path needs Fh % 4 == 0 besides pg_spmm_sum's conditions.
+ * Workspace: pg_spmm_sum_workspace(g, H*Fh). */
+int pg_spmm_sum_heads(const pg_csr_t* g, const float* A, int64_t lda, int32_t H, const float* X,
+                      int64_t ldx, int64_t Fh, float* out, int64_t ldo, void* ws, size_t ws_bytes,
+                      pg_stream_t stream);
+/* de[k,h] = sum_{j < Fh} Dm[v, h*Fh + j] * X[col[k], h*Fh + j]: the gradient of
+ * pg_spmm_sum_heads w.r.t. A (Dm = dout), and apply_edges(u_dot_v) on (N, H, Fh) operands.
+ * The wave-wide path needs Fh in {4, 8, ... 256} and pg_sddmm_dot's vector conditions. */
+int pg_sddmm_dot_heads(const pg_csr_t* g, const float* Dm, int64_t ldd, const float* X,
+                       int64_t ldx, int32_t H, int64_t Fh, float* de, int64_t lde,
+                       pg_stream_t stream);
 
 /* argx[v,f] = col[ptr[v] + argpos[v,f]] (DGL's argX, int64), -1 where none. */
 int pg_argpos_to_src(const pg_csr_t* g, const void* argpos, int64_t lda, int arg_kind,
@@ -489,6 +525,16 @@ int pg_argpos_to_src_cpu(const pg_csr_t* g, const void* argpos, int64_t lda, int
 int pg_sddmm_dot_cpu(const pg_csr_t* g, const float* D, int64_t ldd, const float* X, int64_t ldx,
                      int64_t F, int norm_mode, const void* argpos, int64_t lda, int arg_kind,
                      float* de);
+/* The multi-head entry points on host pointers: row reductions (softmax, sum) in ascending
+ * k, dot products in ascending j, OpenMP over rows; no work schedule, no workspace. */
+int pg_edge_softmax_fwd_cpu(const pg_csr_t* g, const float* s, int64_t lds, int32_t H, float* a,
+                            int64_t lda);
+int pg_edge_softmax_bwd_cpu(const pg_csr_t* g, const float* a, int64_t lda, const float* da,
+                            int64_t ldda, int32_t H, float* ds, int64_t ldds);
+int pg_spmm_sum_heads_cpu(const pg_csr_t* g, const float* A, int64_t lda, int32_t H,
+                          const float* X, int64_t ldx, int64_t Fh, float* out, int64_t ldo);
+int pg_sddmm_dot_heads_cpu(const pg_csr_t* g, const float* Dm, int64_t ldd, const float* X,
+                           int64_t ldx, int32_t H, int64_t Fh, float* de, int64_t lde);
 
 /* ---------------- device: §8f — edge clustering coefficient ---------------- */
 
@@ -568,7 +614,8 @@ int pg_version(void); /* 2: pg_csr_t.einv; 3: pg_spmm_max_bwd fwd_out; 5: no in-
                          indices (transposed max-backward descriptors), pg_gemm_f32_cat;
                          11: pg_pad2d_group; 12: pg_mlp_l1_head;
                          13: pg_mlp_l1_split, pg_mlp_l1_head_ex, pg_adam_apply_l1;
-                         13 also: pg_sddmm_dot */
+                         13 also: pg_sddmm_dot; pg_edge_softmax_fwd / _bwd,
+                         pg_spmm_sum_heads, pg_sddmm_dot_heads and their _cpu twins */
 
 #ifdef __cplusplus
 }

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 
 #include "../../include/plagnn.h"
 
@@ -55,9 +56,35 @@ inline int check_sddmm(const pg_csr_t* g, const char* who, int64_t ldd, int64_t 
   return PG_OK;
 }
 
+// log2 of a power of two, -1 for anything else
+inline int log2_exact(int32_t x) {
+  if (x <= 0 || (x & (x - 1)) != 0) return -1;
+  int l = 0;
+  while ((1 << l) < x) ++l;
+  return l;
+}
+
+// the multi-head entry points ([_cpu] too): 1 <= H <= 64 heads, edge features [nnz][ld >= H]
+// whose nnz * H values are indexed in int32
+inline int check_heads(const pg_csr_t* g, const char* who, int32_t H, std::initializer_list<int64_t> edge_lds) {
+  if (H < 1 || H > 64) return set_error(PG_ERR_INVALID, "%s: H = %d heads, 1 .. 64 supported", who, (int)H);
+  for (int64_t ld : edge_lds)
+    if (ld < H) return set_error(PG_ERR_INVALID, "%s: bad edge leading dims", who);
+  if (g->nnz * H > INT32_MAX) return set_error(PG_ERR_UNSUPPORTED, "%s: nnz * H larger than int32", who);
+  return PG_OK;
+}
+
+// node features [n][ld >= H * Fh], H * Fh within pg_spmm_sum's range
+inline int check_head_features(const char* who, int32_t H, int64_t Fh, std::initializer_list<int64_t> lds) {
+  if (Fh < 1 || Fh > (1 << 30) / H) return set_error(PG_ERR_INVALID, "%s: bad Fh", who);
+  for (int64_t ld : lds)
+    if (ld < H * Fh) return set_error(PG_ERR_INVALID, "%s: bad F/leading dims", who);
+  return PG_OK;
+}
+
 }  // namespace pg
 
-#define PG_TRY(expr)            \
+#define PG_TRY(expr)           \
   do {                          \
     int _rc = (expr);           \
     if (_rc != PG_OK) return _rc; \

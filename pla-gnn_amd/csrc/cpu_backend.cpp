@@ -213,4 +213,97 @@ int pg_sddmm_dot_cpu(const pg_csr_t* g, const float* D, int64_t ldd, const float
   return pg::ok();
 }
 
+// ---- multi-head attention: row reductions in ascending k, dots in ascending j ----------
+int pg_edge_softmax_fwd_cpu(const pg_csr_t* g, const float* s, int64_t lds, int32_t H, float* a, int64_t lda) {
+  PG_TRY(pg::check_csr(g, "pg_edge_softmax_fwd_cpu", false));
+  PG_TRY(pg::check_heads(g, "pg_edge_softmax_fwd_cpu", H, {lds, lda}));
+  if (g->nnz == 0 || g->n_rows == 0) return pg::ok();
+  if (!s || !a) return pg::set_error(PG_ERR_INVALID, "pg_edge_softmax_fwd_cpu: NULL buffer");
+  if (s == a) return pg::set_error(PG_ERR_INVALID, "pg_edge_softmax_fwd_cpu: the output aliases an input");
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t v = 0; v < g->n_rows; ++v) {
+    const int32_t b = g->ptr[v], e = g->ptr[v + 1];
+    for (int32_t h = 0; h < H; ++h) {
+      float m = -std::numeric_limits<float>::infinity();
+      for (int32_t k = b; k < e; ++k) m = std::fmax(m, s[k * lds + h]);
+      float sum = 0.f;
+      for (int32_t k = b; k < e; ++k) {
+        const float t = std::exp(s[k * lds + h] - m);
+        a[k * lda + h] = t;
+        sum += t;
+      }
+      for (int32_t k = b; k < e; ++k) a[k * lda + h] = a[k * lda + h] / sum;
+    }
+  }
+  return pg::ok();
+}
+
+int pg_edge_softmax_bwd_cpu(const pg_csr_t* g, const float* a, int64_t lda, const float* da, int64_t ldda,
+                            int32_t H, float* ds, int64_t ldds) {
+  PG_TRY(pg::check_csr(g, "pg_edge_softmax_bwd_cpu", false));
+  PG_TRY(pg::check_heads(g, "pg_edge_softmax_bwd_cpu", H, {lda, ldda, ldds}));
+  if (g->nnz == 0 || g->n_rows == 0) return pg::ok();
+  if (!a || !da || !ds) return pg::set_error(PG_ERR_INVALID, "pg_edge_softmax_bwd_cpu: NULL buffer");
+  if (ds == a || ds == da)
+    return pg::set_error(PG_ERR_INVALID, "pg_edge_softmax_bwd_cpu: the output aliases an input");
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t v = 0; v < g->n_rows; ++v) {
+    const int32_t b = g->ptr[v], e = g->ptr[v + 1];
+    for (int32_t h = 0; h < H; ++h) {
+      float sum = 0.f;
+      for (int32_t k = b; k < e; ++k) sum += a[k * lda + h] * da[k * ldda + h];
+      for (int32_t k = b; k < e; ++k) ds[k * ldds + h] = a[k * lda + h] * (da[k * ldda + h] - sum);
+    }
+  }
+  return pg::ok();
+}
+
+int pg_spmm_sum_heads_cpu(const pg_csr_t* g, const float* A, int64_t lda, int32_t H, const float* X, int64_t ldx,
+                          int64_t Fh, float* out, int64_t ldo) {
+  PG_TRY(pg::check_csr(g, "pg_spmm_sum_heads_cpu", false));
+  PG_TRY(pg::check_heads(g, "pg_spmm_sum_heads_cpu", H, {lda}));
+  PG_TRY(pg::check_head_features("pg_spmm_sum_heads_cpu", H, Fh, {ldx, ldo}));
+  if (g->n_rows == 0) return pg::ok();
+  if (!X || !out || (g->nnz > 0 && !A)) return pg::set_error(PG_ERR_INVALID, "pg_spmm_sum_heads_cpu: NULL buffer");
+  if (out == X || out == A)
+    return pg::set_error(PG_ERR_INVALID, "pg_spmm_sum_heads_cpu: the output aliases an input");
+  const int64_t F = (int64_t)H * Fh;
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t r = 0; r < g->n_rows; ++r) {
+    float* o = out + r * ldo;
+    for (int64_t f = 0; f < F; ++f) o[f] = 0.f;
+    for (int32_t k = g->ptr[r]; k < g->ptr[r + 1]; ++k) {
+      const float* x = X + (int64_t)g->col[k] * ldx;
+      const float* w = A + (int64_t)(g->eslot ? g->eslot[k] : k) * lda;
+      for (int32_t h = 0; h < H; ++h)
+        for (int64_t j = 0; j < Fh; ++j) o[h * Fh + j] += x[h * Fh + j] * w[h];
+    }
+  }
+  return pg::ok();
+}
+
+int pg_sddmm_dot_heads_cpu(const pg_csr_t* g, const float* Dm, int64_t ldd, const float* X, int64_t ldx,
+                           int32_t H, int64_t Fh, float* de, int64_t lde) {
+  PG_TRY(pg::check_csr(g, "pg_sddmm_dot_heads_cpu", false));
+  PG_TRY(pg::check_heads(g, "pg_sddmm_dot_heads_cpu", H, {lde}));
+  PG_TRY(pg::check_head_features("pg_sddmm_dot_heads_cpu", H, Fh, {ldd, ldx}));
+  if (g->nnz == 0 || g->n_rows == 0) return pg::ok();
+  if (!de || !Dm || !X) return pg::set_error(PG_ERR_INVALID, "pg_sddmm_dot_heads_cpu: NULL buffer");
+  if (de == Dm || de == X)
+    return pg::set_error(PG_ERR_INVALID, "pg_sddmm_dot_heads_cpu: the output aliases an input");
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t v = 0; v < g->n_rows; ++v) {
+    const float* d = Dm + v * ldd;
+    for (int32_t k = g->ptr[v]; k < g->ptr[v + 1]; ++k) {
+      const float* x = X + (int64_t)g->col[k] * ldx;
+      for (int32_t h = 0; h < H; ++h) {
+        float acc = 0.f;
+        for (int64_t j = 0; j < Fh; ++j) acc += d[h * Fh + j] * x[h * Fh + j];
+        de[(int64_t)k * lde + h] = acc;
+      }
+    }
+  }
+  return pg::ok();
+}
+
 }  // extern "C"

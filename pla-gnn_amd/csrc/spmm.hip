@@ -1573,6 +1573,368 @@ __global__ __launch_bounds__(kBlock) void sddmm_dot_kernel(
   }
 }
 
+// ---- multi-head attention: edge softmax, per-head weighted sum, per-head SDDMM ----------
+// Edge features are [nnz][ld] in in-CSR slot order, H <= 64 heads per edge.
+//
+// Edge softmax (forward and backward): a row the schedule keeps whole takes one wave, a row
+// it splits (exactly the rows of `merges`) one 256-thread workgroup, the first n_merges
+// workgroups of the launch; the other workgroups walk the items and skip the pieces of split
+// rows. With H a power of two (lg = log2 H) a thread covers the row's deg * H values at
+// i = tid, tid + NT, ...: its head i & (H - 1) never changes (NT % H == 0), so a reduction
+// over the row is a per-thread running value, xor-shuffles of stride H, 2H, ... 32 across the
+// lanes of equal head and, in a workgroup, one pass over the four waves' results in LDS in
+// wave order. Any other H goes one head at a time through the same code (lg = 0 on a base
+// pointer moved to the head, values ld apart). A whole row of at most 64 * kSmR values stays
+// in registers between the passes (read once, written once); longer rows re-read their
+// values, in loops unrolled by 4 so that four loads per thread are in flight (the longest
+// split row bounds the call: cfg2 forward 36 -> 27 us). No workspace, no
+// atomics; the order of every reduction depends on (deg, H) only.
+constexpr int kSmR = 4;
+
+__device__ __forceinline__ int64_t esm_off(int i, int lg, int64_t ld) {
+  return (int64_t)(i >> lg) * ld + (i & ((1 << lg) - 1));
+}
+
+// reduction over the threads of equal head: lanes `stride0` apart inside the wave, then (BLOCK)
+// the four waves in order through red[wave][head]; every thread gets its head's result
+template <bool MAX, bool BLOCK>
+__device__ __forceinline__ float esm_reduce(float x, int stride0, float (*red)[kWave]) {
+  for (int o = stride0; o < kWave; o <<= 1) {
+    const float y = __shfl_xor(x, o);
+    x = MAX ? fmaxf(x, y) : x + y;
+  }
+  if constexpr (BLOCK) {
+    const int lane = lane_id();
+    if (lane < stride0) red[threadIdx.x >> 6][lane] = x;
+    __syncthreads();
+    const int h = lane & (stride0 - 1);
+    x = red[0][h];
+#pragma unroll
+    for (int q = 1; q < kWavesPerBlock; ++q) x = MAX ? fmaxf(x, red[q][h]) : x + red[q][h];
+  }
+  return x;
+}
+
+// a[i] = exp(s[i] - m) / sum over the n = deg << lg values of one row (s, a at its first slot)
+template <bool BLOCK>
+__device__ __forceinline__ void esm_fwd_row(const float* __restrict__ s, int64_t lds, float* __restrict__ a,
+                                            int64_t lda, int n, int lg, float (*rmax)[kWave],
+                                            float (*rsum)[kWave]) {
+  constexpr int NT = BLOCK ? kBlock : kWave;
+  const int tid = BLOCK ? (int)threadIdx.x : lane_id();
+  const float ninf = -std::numeric_limits<float>::infinity();
+  const bool in_regs = !BLOCK && n <= NT * kSmR;  // uniform
+  float v[kSmR];
+  float m = ninf;
+  if (in_regs) {
+#pragma unroll
+    for (int t = 0; t < kSmR; ++t) {
+      const int i = tid + t * NT;
+      v[t] = i < n ? s[esm_off(i, lg, lds)] : ninf;
+      m = fmaxf(m, v[t]);
+    }
+  } else {
+#pragma unroll 4
+    for (int i = tid; i < n; i += NT) m = fmaxf(m, s[esm_off(i, lg, lds)]);
+  }
+  m = esm_reduce<true, BLOCK>(m, 1 << lg, rmax);
+  float sum = 0.f;
+  if (in_regs) {
+#pragma unroll
+    for (int t = 0; t < kSmR; ++t) {
+      v[t] = expf(v[t] - m);  // -inf (a masked score, a lane past the row): exactly 0
+      sum += v[t];
+    }
+  } else {
+#pragma unroll 4
+    for (int i = tid; i < n; i += NT) sum += expf(s[esm_off(i, lg, lds)] - m);
+  }
+  sum = esm_reduce<false, BLOCK>(sum, 1 << lg, rsum);
+  if (in_regs) {
+#pragma unroll
+    for (int t = 0; t < kSmR; ++t) {
+      const int i = tid + t * NT;
+      if (i < n) a[esm_off(i, lg, lda)] = v[t] / sum;
+    }
+  } else {
+#pragma unroll 4
+    for (int i = tid; i < n; i += NT) a[esm_off(i, lg, lda)] = expf(s[esm_off(i, lg, lds)] - m) / sum;
+  }
+}
+
+// ds[i] = a[i] * (da[i] - sum_row a * da)
+template <bool BLOCK>
+__device__ __forceinline__ void esm_bwd_row(const float* __restrict__ a, int64_t lda, const float* __restrict__ da,
+                                            int64_t ldda, float* __restrict__ ds, int64_t ldds, int n, int lg,
+                                            float (*rsum)[kWave]) {
+  constexpr int NT = BLOCK ? kBlock : kWave;
+  const int tid = BLOCK ? (int)threadIdx.x : lane_id();
+  const bool in_regs = !BLOCK && n <= NT * kSmR;  // uniform
+  float va[kSmR], vd[kSmR];
+  float sum = 0.f;
+  if (in_regs) {
+#pragma unroll
+    for (int t = 0; t < kSmR; ++t) {
+      const int i = tid + t * NT;
+      va[t] = i < n ? a[esm_off(i, lg, lda)] : 0.f;
+      vd[t] = i < n ? da[esm_off(i, lg, ldda)] : 0.f;
+      sum += va[t] * vd[t];
+    }
+  } else {
+#pragma unroll 4
+    for (int i = tid; i < n; i += NT) sum += a[esm_off(i, lg, lda)] * da[esm_off(i, lg, ldda)];
+  }
+  sum = esm_reduce<false, BLOCK>(sum, 1 << lg, rsum);
+  if (in_regs) {
+#pragma unroll
+    for (int t = 0; t < kSmR; ++t) {
+      const int i = tid + t * NT;
+      if (i < n) ds[esm_off(i, lg, ldds)] = va[t] * (vd[t] - sum);
+    }
+  } else {
+#pragma unroll 4
+    for (int i = tid; i < n; i += NT)
+      ds[esm_off(i, lg, ldds)] = a[esm_off(i, lg, lda)] * (da[esm_off(i, lg, ldda)] - sum);
+  }
+}
+
+// The row of this wave (whole-row items) or workgroup (split rows): false = nothing to do.
+// lg >= 0: H = 1 << lg; lg < 0: any H, one head at a time.
+__device__ __forceinline__ bool esm_row(const int32_t* __restrict__ ptr, const int4* __restrict__ items, int n_items,
+                                        const int4* __restrict__ merges, int n_merges, int& rs, int& deg) {
+  if ((int)blockIdx.x < n_merges) {
+    const int row = merges[blockIdx.x].x;
+    rs = ptr[row];
+    deg = ptr[row + 1] - rs;
+    return true;
+  }
+  const int it = ((int)blockIdx.x - n_merges) * kWavesPerBlock + wave_id_uniform();
+  if (it >= n_items) return false;
+  const int4 item = items[it];
+  if (item.w >= 0) return false;  // a piece of a split row: taken whole by a workgroup
+  rs = item.y;
+  deg = item.z - item.y;
+  return deg > 0;
+}
+
+__global__ __launch_bounds__(kBlock) void edge_softmax_fwd_kernel(
+    const int32_t* __restrict__ ptr, const int4* __restrict__ items, int n_items, const int4* __restrict__ merges,
+    int n_merges, const float* __restrict__ s, int64_t lds, float* __restrict__ a, int64_t lda, int H, int lg) {
+  __shared__ float rmax[kWavesPerBlock][kWave], rsum[kWavesPerBlock][kWave];
+  int rs, deg;
+  if (!esm_row(ptr, items, n_items, merges, n_merges, rs, deg)) return;
+  s += (int64_t)rs * lds;
+  a += (int64_t)rs * lda;
+  if ((int)blockIdx.x < n_merges) {  // uniform over the workgroup
+    if (lg >= 0) {
+      esm_fwd_row<true>(s, lds, a, lda, deg << lg, lg, rmax, rsum);
+    } else {
+      for (int h = 0; h < H; ++h) {
+        esm_fwd_row<true>(s + h, lds, a + h, lda, deg, 0, rmax, rsum);
+        __syncthreads();  // rmax / rsum are reused by the next head
+      }
+    }
+  } else if (lg >= 0) {
+    esm_fwd_row<false>(s, lds, a, lda, deg << lg, lg, rmax, rsum);
+  } else {
+    for (int h = 0; h < H; ++h) esm_fwd_row<false>(s + h, lds, a + h, lda, deg, 0, rmax, rsum);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void edge_softmax_bwd_kernel(
+    const int32_t* __restrict__ ptr, const int4* __restrict__ items, int n_items, const int4* __restrict__ merges,
+    int n_merges, const float* __restrict__ a, int64_t lda, const float* __restrict__ da, int64_t ldda,
+    float* __restrict__ ds, int64_t ldds, int H, int lg) {
+  __shared__ float rsum[kWavesPerBlock][kWave];
+  int rs, deg;
+  if (!esm_row(ptr, items, n_items, merges, n_merges, rs, deg)) return;
+  a += (int64_t)rs * lda;
+  da += (int64_t)rs * ldda;
+  ds += (int64_t)rs * ldds;
+  if ((int)blockIdx.x < n_merges) {  // uniform over the workgroup
+    if (lg >= 0) {
+      esm_bwd_row<true>(a, lda, da, ldda, ds, ldds, deg << lg, lg, rsum);
+    } else {
+      for (int h = 0; h < H; ++h) {
+        esm_bwd_row<true>(a + h, lda, da + h, ldda, ds + h, ldds, deg, 0, rsum);
+        __syncthreads();  // rsum is reused by the next head
+      }
+    }
+  } else if (lg >= 0) {
+    esm_bwd_row<false>(a, lda, da, ldda, ds, ldds, deg << lg, lg, rsum);
+  } else {
+    for (int h = 0; h < H; ++h) esm_bwd_row<false>(a + h, lda, da + h, ldda, ds + h, ldds, deg, 0, rsum);
+  }
+}
+
+// Per-head weighted sum: sum_kernel with the weight A[slot, head of the column] in place of
+// ew[slot]. The launch covers the columns [f0, f0 + F) of the H * Fh (X, out, ws point at
+// column f0): a lane's head comes from its absolute column, once per column chunk, so a head
+// may straddle two launches' tiles. On the vector path (Fh % 4 == 0) a lane's four columns
+// share one head. The U edges' weights are fetched beside their X rows (one 4-byte load per
+// lane and chunk; the lanes of a head read one address), so the loads of a batch are all in
+// flight together. Split rows leave partial sums in ws for sum_merge_kernel, as sum_kernel.
+template <int W, int NC>
+__global__ __launch_bounds__(kBlock) void sum_heads_kernel(
+    const int32_t* __restrict__ col, const int32_t* __restrict__ eslot, const float* __restrict__ A,
+    int64_t lda, int H, int Fh, int f0, const int4* __restrict__ items, int n_items,
+    const float* __restrict__ X, int64_t ldx, int F, float* __restrict__ out, int64_t ldo,
+    float* __restrict__ ws, int64_t ldw) {
+  constexpr int U = EdgeU<W, NC>::value;
+  const int it = blockIdx.x * kWavesPerBlock + wave_id_uniform();
+  if (it >= n_items) return;
+  const int4 item = items[it];
+  const int row = item.x, k0 = item.y, k1 = item.z, slot = item.w;
+  const int lane = lane_id();
+  float acc[NC][W];
+  int hc[NC];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    hc[c] = min((f0 + (c * kWave + lane) * W) / Fh, H - 1);  // lanes past F: a valid head, result not stored
+#pragma unroll
+    for (int i = 0; i < W; ++i) acc[c][i] = 0.f;
+  }
+
+  for (int kw = k0; kw < k1; kw += kWave) {
+    const int nw = min(kWave, k1 - kw);
+    const int kl = kw + min(lane, nw - 1);
+    const int idxv = col[kl];
+    const int sv = eslot ? eslot[kl] : kl;
+    for (int j = 0; j < nw; j += U) {
+      const int nv = min(U, nw - j);
+      float v[U][NC][W];
+      float w[U][NC];
+#pragma unroll
+      for (int e = 0; e < U; ++e) {
+        const int je = j + min(e, nv - 1);
+        const float* xr = X + (int64_t)bcast(idxv, je) * ldx;
+        const float* ar = A + (int64_t)bcast(sv, je) * lda;
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+          load_tile<W>(xr, (c * kWave + lane) * W, F, v[e][c], 0.f);
+          w[e][c] = ar[hc[c]];
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < U; ++e) {
+        if (e < nv) {
+#pragma unroll
+          for (int c = 0; c < NC; ++c)
+#pragma unroll
+            for (int i = 0; i < W; ++i) acc[c][i] += v[e][c][i] * w[e][c];
+        }
+      }
+    }
+  }
+  float* orow = slot < 0 ? out + (int64_t)row * ldo : ws + (int64_t)slot * ldw;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) store_tile<W>(orow, (c * kWave + lane) * W, F, acc[c]);
+}
+
+// Per-head SDDMM, vector path with Fh / 4 = 1 << LGL lanes per head (Fh = 4 ... 256):
+// sddmm_dot_kernel with the cross-lane reduction stopped at the head boundary. Of the
+// transposing butterfly's three steps the first TS = min(3, LGL) stay inside a head; plain
+// steps cover the head's remaining lane bits. A lane then holds 8 >> TS sums: those of the
+// batch's edges (i << TS) + (lane & (2^TS - 1)) for the head of its columns. A head lies in
+// exactly one 256-column tile, so nothing is carried between tiles; one lane per (edge, head)
+// stores, a batch's H values per edge side by side.
+template <int LGL>
+__global__ __launch_bounds__(kBlock) void sddmm_heads_kernel(
+    const int32_t* __restrict__ col, const int4* __restrict__ items, int n_items,
+    const float* __restrict__ D, int64_t ldd, const float* __restrict__ X, int64_t ldx, int F,
+    float* __restrict__ de, int64_t lde) {
+  constexpr int U = 8, W = 4;
+  constexpr int T = kWave * W;
+  constexpr int TS = LGL < 3 ? LGL : 3;
+  constexpr int LPH = 1 << LGL;  // lanes per head
+  const int it = blockIdx.x * kWavesPerBlock + wave_id_uniform();
+  if (it >= n_items) return;
+  const int4 item = items[it];
+  const int row = item.x, k0 = item.y, k1 = item.z;
+  const int lane = lane_id();
+  const float* drow = D + (int64_t)row * ldd;
+  const bool one_tile = F <= T;
+  float d[W] = {0.f, 0.f, 0.f, 0.f};
+  if (one_tile) load_tile<W>(drow, lane * W, F, d, 0.f);
+  const bool b0 = lane & 1, b1 = lane & 2, b2 = lane & 4;
+  const int esub = lane & ((1 << TS) - 1);        // the lane's edge inside a group of 1 << TS
+  const bool writer = (lane & (LPH - 1)) == esub;  // one lane per (edge, head)
+
+  for (int kw = k0; kw < k1; kw += kWave) {
+    const int nw = min(kWave, k1 - kw);
+    const int idxv = col[kw + min(lane, nw - 1)];
+    for (int f0 = 0; f0 < F; f0 += T) {
+      const int f = f0 + lane * W;
+      if (!one_tile) load_tile<W>(drow, f, F, d, 0.f);
+      const int head = f >> (LGL + 2);
+      for (int j = 0; j < nw; j += U) {
+        const int nv = min(U, nw - j);
+        float v[U][W];
+#pragma unroll
+        for (int e = 0; e < U; ++e)
+          load_tile<W>(X + (int64_t)bcast(idxv, j + min(e, nv - 1)) * ldx, f, F, v[e], 0.f);
+        float p[U];
+#pragma unroll
+        for (int e = 0; e < U; ++e) {
+          float s = 0.f;
+#pragma unroll
+          for (int i = 0; i < W; ++i) s += d[i] * v[e][i];
+          p[e] = s;
+        }
+        if constexpr (TS >= 1) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            const float keep = b0 ? p[2 * i + 1] : p[2 * i], send = b0 ? p[2 * i] : p[2 * i + 1];
+            p[i] = keep + __shfl_xor(send, 1);
+          }
+        }
+        if constexpr (TS >= 2) {
+#pragma unroll
+          for (int i = 0; i < 2; ++i) {
+            const float keep = b1 ? p[2 * i + 1] : p[2 * i], send = b1 ? p[2 * i] : p[2 * i + 1];
+            p[i] = keep + __shfl_xor(send, 2);
+          }
+        }
+        if constexpr (TS >= 3) {
+          const float keep = b2 ? p[1] : p[0], send = b2 ? p[0] : p[1];
+          p[0] = keep + __shfl_xor(send, 4);
+#pragma unroll
+          for (int o = 8; o < LPH; o <<= 1) p[0] += __shfl_xor(p[0], o);
+        }
+        if (writer && f < F) {
+#pragma unroll
+          for (int i = 0; i < (U >> TS); ++i) {
+            const int e = (i << TS) + esub;
+            if (e < nv) de[(int64_t)(kw + j + e) * lde + head] = p[i];
+          }
+        }
+      }
+    }
+  }
+}
+
+// Any other Fh, or unaligned operands: one (edge, head) pair per lane, Fh products in
+// ascending j (the host entry point's order).
+__global__ __launch_bounds__(kBlock) void sddmm_heads_generic_kernel(
+    const int32_t* __restrict__ col, const int4* __restrict__ items, int n_items,
+    const float* __restrict__ D, int64_t ldd, const float* __restrict__ X, int64_t ldx, int H, int Fh,
+    float* __restrict__ de, int64_t lde) {
+  const int it = blockIdx.x * kWavesPerBlock + wave_id_uniform();
+  if (it >= n_items) return;
+  const int4 item = items[it];
+  const int row = item.x, k0 = item.y, k1 = item.z;
+  const float* drow = D + (int64_t)row * ldd;
+  const int64_t n = (int64_t)(k1 - k0) * H;
+  for (int64_t i = lane_id(); i < n; i += kWave) {
+    const int k = k0 + (int)(i / H), h = (int)(i % H);
+    const float* dh = drow + (int64_t)h * Fh;
+    const float* xh = X + (int64_t)col[k] * ldx + (int64_t)h * Fh;
+    float acc = 0.f;
+    for (int j = 0; j < Fh; ++j) acc += dh[j] * xh[j];
+    de[(int64_t)k * lde + h] = acc;
+  }
+}
+
 // ---- DGL-form scatter backward (float atomics) ----------------------------------------
 __global__ __launch_bounds__(kBlock) void clear_u4_kernel(uint4* __restrict__ x, int64_t n4) {
   for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n4; i += (int64_t)gridDim.x * kBlock)
@@ -2236,6 +2598,110 @@ int pg_sddmm_dot(const pg_csr_t* g, const float* D, int64_t ldd, const float* X,
   if (tp.vec) by_form(std::integral_constant<int, 4>{});
   else by_form(std::integral_constant<int, 1>{});
   return hip_status("pg_sddmm_dot");
+}
+
+int pg_edge_softmax_fwd(const pg_csr_t* g, const float* s, int64_t lds, int32_t H, float* a, int64_t lda,
+                        pg_stream_t stream) {
+  PG_TRY(pg::check_csr(g, "pg_edge_softmax_fwd", true));
+  PG_TRY(pg::check_heads(g, "pg_edge_softmax_fwd", H, {lds, lda}));
+  if (g->nnz == 0 || g->n_rows == 0) return pg::ok();
+  if (!s || !a) return pg::set_error(PG_ERR_INVALID, "pg_edge_softmax_fwd: NULL buffer");
+  if (s == a) return pg::set_error(PG_ERR_INVALID, "pg_edge_softmax_fwd: the output aliases an input");
+  const int blocks = (int)g->n_merges + grid_for(g->n_items);
+  hipLaunchKernelGGL(edge_softmax_fwd_kernel, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g->ptr,
+                     (const int4*)g->items, (int)g->n_items, (const int4*)g->merges, (int)g->n_merges, s, lds, a,
+                     lda, (int)H, pg::log2_exact(H));
+  return hip_status("pg_edge_softmax_fwd");
+}
+
+int pg_edge_softmax_bwd(const pg_csr_t* g, const float* a, int64_t lda, const float* da, int64_t ldda, int32_t H,
+                        float* ds, int64_t ldds, pg_stream_t stream) {
+  PG_TRY(pg::check_csr(g, "pg_edge_softmax_bwd", true));
+  PG_TRY(pg::check_heads(g, "pg_edge_softmax_bwd", H, {lda, ldda, ldds}));
+  if (g->nnz == 0 || g->n_rows == 0) return pg::ok();
+  if (!a || !da || !ds) return pg::set_error(PG_ERR_INVALID, "pg_edge_softmax_bwd: NULL buffer");
+  if (ds == a || ds == da) return pg::set_error(PG_ERR_INVALID, "pg_edge_softmax_bwd: the output aliases an input");
+  const int blocks = (int)g->n_merges + grid_for(g->n_items);
+  hipLaunchKernelGGL(edge_softmax_bwd_kernel, dim3(blocks), dim3(kBlock), 0, (hipStream_t)stream, g->ptr,
+                     (const int4*)g->items, (int)g->n_items, (const int4*)g->merges, (int)g->n_merges, a, lda, da,
+                     ldda, ds, ldds, (int)H, pg::log2_exact(H));
+  return hip_status("pg_edge_softmax_bwd");
+}
+
+int pg_spmm_sum_heads(const pg_csr_t* g, const float* A, int64_t lda, int32_t H, const float* X, int64_t ldx,
+                      int64_t Fh, float* out, int64_t ldo, void* ws, size_t ws_bytes, pg_stream_t stream) {
+  PG_TRY(pg::check_csr(g, "pg_spmm_sum_heads", true));
+  PG_TRY(pg::check_heads(g, "pg_spmm_sum_heads", H, {lda}));
+  PG_TRY(pg::check_head_features("pg_spmm_sum_heads", H, Fh, {ldx, ldo}));
+  if (g->n_rows == 0) return pg::ok();  // (nnz == 0 with rows: every row is empty, out = 0)
+  const int64_t F = (int64_t)H * Fh;
+  if (!X || !out || (g->nnz > 0 && !A)) return pg::set_error(PG_ERR_INVALID, "pg_spmm_sum_heads: NULL buffer");
+  if (out == X || out == A) return pg::set_error(PG_ERR_INVALID, "pg_spmm_sum_heads: the output aliases an input");
+  const size_t need = pg_spmm_sum_workspace(g, F);
+  PG_TRY(check_ws(ws_bytes, need, "pg_spmm_sum_heads"));
+  float* w = need ? (float*)ws : nullptr;
+  const int64_t ldw = ws_ld(F);
+  hipStream_t st = (hipStream_t)stream;
+  TilePlan tp = plan_tiles(F, {ldx, ldo}, {X, out, w});
+  if (Fh % 4 != 0) tp = {false, (int64_t)kFTileScalar};  // a lane's four columns must share a head
+  const int blocks = grid_for(g->n_items);
+  for (int64_t f0 = 0; f0 < F; f0 += tp.tile) {
+    const int Ft = (int)std::min<int64_t>(tp.tile, F - f0);
+    auto go = [&](auto nc_c, auto w_c) -> int {
+      constexpr int NC = decltype(nc_c)::value;
+      constexpr int W = decltype(w_c)::value;
+      hipLaunchKernelGGL((sum_heads_kernel<W, NC>), dim3(blocks), dim3(kBlock), 0, st, g->col, g->eslot, A, lda,
+                         (int)H, (int)Fh, (int)f0, (const int4*)g->items, (int)g->n_items, X + f0, ldx, Ft,
+                         out + f0, ldo, w ? w + f0 : nullptr, ldw);
+      return PG_OK;
+    };
+    int rc;
+    if (tp.vec)
+      rc = dispatch_nc_vec((Ft + 255) / 256, [&](auto n) { return go(n, std::integral_constant<int, 4>{}); });
+    else
+      rc = dispatch_nc_scalar((Ft + 63) / 64, [&](auto n) { return go(n, std::integral_constant<int, 1>{}); });
+    if (rc != PG_OK) return pg::set_error(rc, "pg_spmm_sum_heads: unsupported feature tile");
+    if (g->n_merges > 0)
+      hipLaunchKernelGGL(sum_merge_kernel<float>, dim3((unsigned)g->n_merges), dim3(kBlock), 0, st,
+                         (const int4*)g->merges, (int)g->n_merges, Ft, w + f0, ldw, g->ptr, 0, nullptr, 0,
+                         out + f0, ldo);
+  }
+  return hip_status("pg_spmm_sum_heads");
+}
+
+int pg_sddmm_dot_heads(const pg_csr_t* g, const float* Dm, int64_t ldd, const float* X, int64_t ldx, int32_t H,
+                       int64_t Fh, float* de, int64_t lde, pg_stream_t stream) {
+  PG_TRY(pg::check_csr(g, "pg_sddmm_dot_heads", true));
+  PG_TRY(pg::check_heads(g, "pg_sddmm_dot_heads", H, {lde}));
+  PG_TRY(pg::check_head_features("pg_sddmm_dot_heads", H, Fh, {ldd, ldx}));
+  if (g->nnz == 0 || g->n_rows == 0) return pg::ok();
+  if (!de || !Dm || !X) return pg::set_error(PG_ERR_INVALID, "pg_sddmm_dot_heads: NULL buffer");
+  if (de == Dm || de == X) return pg::set_error(PG_ERR_INVALID, "pg_sddmm_dot_heads: the output aliases an input");
+  const int64_t F = (int64_t)H * Fh;
+  const TilePlan tp = plan_tiles(F, {ldd, ldx}, {Dm, X});
+  const int lgl = (Fh % 4 == 0) ? pg::log2_exact((int32_t)std::min<int64_t>(Fh / 4, 1 << 20)) : -1;
+  const int blocks = grid_for(g->n_items);
+  hipStream_t st = (hipStream_t)stream;
+  auto go = [&](auto l_c) {
+    constexpr int LGL = decltype(l_c)::value;
+    hipLaunchKernelGGL((sddmm_heads_kernel<LGL>), dim3(blocks), dim3(kBlock), 0, st, g->col, (const int4*)g->items,
+                       (int)g->n_items, Dm, ldd, X, ldx, (int)F, de, lde);
+  };
+  if (tp.vec && lgl >= 0 && lgl <= 6) {
+    switch (lgl) {
+      case 0: go(std::integral_constant<int, 0>{}); break;
+      case 1: go(std::integral_constant<int, 1>{}); break;
+      case 2: go(std::integral_constant<int, 2>{}); break;
+      case 3: go(std::integral_constant<int, 3>{}); break;
+      case 4: go(std::integral_constant<int, 4>{}); break;
+      case 5: go(std::integral_constant<int, 5>{}); break;
+      default: go(std::integral_constant<int, 6>{}); break;
+    }
+  } else {
+    hipLaunchKernelGGL(sddmm_heads_generic_kernel, dim3(blocks), dim3(kBlock), 0, st, g->col,
+                       (const int4*)g->items, (int)g->n_items, Dm, ldd, X, ldx, (int)H, (int)Fh, de, lde);
+  }
+  return hip_status("pg_sddmm_dot_heads");
 }
 
 int pg_argpos_to_src(const pg_csr_t* g, const void* argpos, int64_t lda, int arg_kind,

@@ -14,7 +14,10 @@ The reference touches exactly this surface:
 plus ``update_all`` with ``dgl.function`` builtins (copy_u / u_mul_e with sum / mean /
 max), which SAGEConv itself is defined by, and ``apply_edges`` with ``u_dot_v`` (DGL's
 SDDMM). Edge weights may require grad: every weighted aggregation is differentiable with
-respect to them, as DGL's GSpMM.backward is.
+respect to them, as DGL's GSpMM.backward is. Multi-head attention (reference-unpinned):
+``apply_edges(u_add_v)``, ``dgl.ops.edge_softmax`` / ``dgl.nn.functional.edge_softmax``,
+``u_dot_v`` and ``update_all(u_mul_e, sum)`` on (N, H, Fh) features with (E, H, 1) edge
+features, and ``dgl.nn.pytorch.GATConv`` built on them.
 
 Message passing on a CUDA (HIP) device always runs in libplagnn.so; a missing library is
 an error, never a silent fallback.
@@ -28,6 +31,7 @@ import numpy as np
 import torch
 
 from . import function  # noqa: F401  (dgl.function)
+from . import ops  # noqa: F401  (dgl.ops)
 from . import nn  # noqa: F401  (dgl.nn)
 
 __version__ = "0.8.2+plagnn"
@@ -236,7 +240,10 @@ class DGLGraph:
             ew = self.edata[message_func.rhs]
             if ew.dim() > 1:
                 if ew.numel() != ew.shape[0]:
-                    raise NotImplementedError("u_mul_e with multi-dimensional edge features")
+                    self._update_all_heads(X, ew, reduce_func)
+                    if apply_node_func is not None:
+                        self.ndata.update(apply_node_func(_NodeBatch(self)))
+                    return
                 ew = ew.reshape(-1)
         shape = X.shape
         X2 = X.reshape(shape[0], -1)
@@ -252,23 +259,59 @@ class DGLGraph:
         if apply_node_func is not None:
             self.ndata.update(apply_node_func(_NodeBatch(self)))
 
+    def _update_all_heads(self, X, ew, reduce_func):
+        """update_all(u_mul_e, sum) with (N, H, Fh) features and (E, H, 1) weights, H > 1:
+        GATConv's aggregation, the engine's pg_spmm_sum_heads."""
+        if X.dim() != 3 or ew.dim() != 3 or ew.shape[2] != 1:
+            raise NotImplementedError("u_mul_e with multi-dimensional edge features: (N, H, Fh) node "
+                                      "features with (E, H, 1) edge features are supported")
+        if ew.shape[1] != X.shape[1]:
+            raise ValueError(f"u_mul_e: {X.shape[1]} heads of node features, {ew.shape[1]} of edge features")
+        if reduce_func.op != "sum":
+            raise NotImplementedError(f"u_mul_e with multi-head edge features supports sum, not {reduce_func.op}")
+        n, H, Fh = X.shape
+        dg = self._device_graph(X.device)
+        A = dg.edge_weight_slots(ew)
+        out = _engine().ops.SumAggregateHeads.apply(X.reshape(n, H * Fh).float(), dg, A, H)
+        self.ndata[reduce_func.out] = out.to(X.dtype).reshape(n, H, Fh)
+
+    def _uv(self, device):
+        """(src, dst) per edge id on `device`, uploaded once per device."""
+        key = ("uv", str(device))
+        if key not in self._csr_cache:
+            self._csr_cache[key] = (self._src.to(device), self._dst.to(device))
+        return self._csr_cache[key]
+
     def apply_edges(self, func, edges=None, etype=None):
         """apply_edges(dgl.function.u_dot_v(lhs, rhs, out)): edata[out][e] = the dot product of
-        ndata[lhs][src_e] and ndata[rhs][dst_e], shape (E, 1), in edge-id order (DGL's SDDMM,
-        the engine's pg_sddmm_dot)."""
+        ndata[lhs][src_e] and ndata[rhs][dst_e] in edge-id order (DGL's SDDMM): shape (E, 1)
+        for 2-D operands (pg_sddmm_dot), (E, H, 1) for (N, H, Fh) operands (pg_sddmm_dot_heads).
+        apply_edges(dgl.function.u_add_v(lhs, rhs, out)): edata[out][e] = ndata[lhs][src_e] +
+        ndata[rhs][dst_e], any trailing shape."""
         from .function import _Message
 
-        if not isinstance(func, _Message) or func.op != "u_dot_v" or edges is not None:
-            raise NotImplementedError("apply_edges supports dgl.function.u_dot_v on all edges only")
+        if not isinstance(func, _Message) or func.op not in ("u_dot_v", "u_add_v") or edges is not None:
+            raise NotImplementedError("apply_edges supports dgl.function.u_dot_v and u_add_v on all edges only")
         lhs, rhs = self.ndata[func.lhs], self.ndata[func.rhs]
         if lhs.shape != rhs.shape:
-            raise ValueError(f"u_dot_v: operand shapes {tuple(lhs.shape)} and {tuple(rhs.shape)} differ")
+            raise ValueError(f"{func.op}: operand shapes {tuple(lhs.shape)} and {tuple(rhs.shape)} differ")
         dg = self._device_graph(lhs.device)
         n = lhs.shape[0]
-        de = _engine().ops.EdgeDot.apply(lhs.reshape(n, -1).float(), rhs.reshape(n, -1).float(), dg)
+        ops = _engine().ops
+        if func.op == "u_add_v":
+            src, dst = self._uv(lhs.device)
+            out = ops.EdgeAdd.apply(lhs.reshape(n, -1).float(), rhs.reshape(n, -1).float(), dg, src, dst)
+            self.edata[func.out] = out.to(lhs.dtype).reshape((-1,) + tuple(lhs.shape[1:]))
+            return
+        if lhs.dim() == 3 and lhs.shape[1] > 1:
+            H = lhs.shape[1]
+            de = ops.EdgeDotHeads.apply(lhs.reshape(n, -1).float(), rhs.reshape(n, -1).float(), dg, H)
+        else:
+            de = ops.EdgeDot.apply(lhs.reshape(n, -1).float(), rhs.reshape(n, -1).float(), dg)
         # slot order -> edge-id order: eid is a permutation, so every element is written once
         out = torch.empty_like(de).index_copy(0, dg.eid, de)
-        self.edata[func.out] = out.to(lhs.dtype).reshape(-1, 1)
+        shape = (-1, lhs.shape[1], 1) if lhs.dim() == 3 else (-1, 1)
+        self.edata[func.out] = out.to(lhs.dtype).reshape(shape)
 
     def __repr__(self):
         return (f"Graph(num_nodes={self._n}, num_edges={self.num_edges()},\n"
@@ -330,4 +373,4 @@ def remove_self_loop(g: DGLGraph, etype=None) -> DGLGraph:
     return ng
 
 
-__all__ = ["DGLGraph", "graph", "add_self_loop", "remove_self_loop", "seed", "function", "nn"]
+__all__ = ["DGLGraph", "graph", "add_self_loop", "remove_self_loop", "seed", "function", "nn", "ops"]

@@ -1,6 +1,7 @@
 """dgl.function builtins understood by DGLGraph.update_all (the forms SAGEConv uses:
 copy_u('h', 'm') / u_mul_e('h', '_edge_weight', 'm') with sum / mean / max) and by
-DGLGraph.apply_edges (u_dot_v('a', 'b', 'out'), DGL's SDDMM)."""
+DGLGraph.apply_edges (u_dot_v('a', 'b', 'out'), DGL's SDDMM, and u_add_v('a', 'b', 'out'),
+GATConv's attention logits)."""
 from __future__ import annotations
 
 
@@ -28,6 +29,11 @@ def u_mul_e(lhs_field: str, rhs_field: str, out: str) -> _Message:
 def u_dot_v(lhs_field: str, rhs_field: str, out: str) -> _Message:
     """out[e] = <ndata[lhs][src_e], ndata[rhs][dst_e]>, shape (E, 1) (apply_edges only)."""
     return _Message("u_dot_v", lhs_field, rhs_field, out)
+
+
+def u_add_v(lhs_field: str, rhs_field: str, out: str) -> _Message:
+    """out[e] = ndata[lhs][src_e] + ndata[rhs][dst_e], any trailing shape (apply_edges only)."""
+    return _Message("u_add_v", lhs_field, rhs_field, out)
 
 
 def sum(msg: str, out: str) -> _Reduce:  # noqa: A001  (DGL's name)

@@ -1,5 +1,5 @@
-"""dgl.nn.pytorch: SAGEConv (the reference's layer, code/model.py:7, 13-15) and GraphConv,
-with DGL 0.8.2's constructor signatures, parameter names and initialisation, computed by
+"""dgl.nn.pytorch: SAGEConv (the reference's layer, code/model.py:7, 13-15), GraphConv and
+GATConv, with DGL 0.8.2's constructor signatures, parameter names and initialisation, computed by
 the plagnn engine."""
 from __future__ import annotations
 
@@ -157,4 +157,86 @@ class GraphConv(nn.Module):
         return rst
 
 
-__all__ = ["SAGEConv", "GraphConv"]
+class GATConv(nn.Module):
+    """DGL 0.8.2 ``GATConv(in_feats, out_feats, num_heads, feat_drop=0., attn_drop=0.,
+    negative_slope=0.2, residual=False, activation=None, allow_zero_in_degree=False,
+    bias=True)``, its forward written as DGL writes it on the shim's own primitives:
+    apply_edges(u_add_v), edge_softmax and update_all(u_mul_e, sum), which run on the engine's
+    multi-head kernels. Not used by the reference: reference-unpinned."""
+
+    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, attn_drop=0.0, negative_slope=0.2,
+                 residual=False, activation=None, allow_zero_in_degree=False, bias=True):
+        super().__init__()
+        if isinstance(in_feats, tuple):
+            raise NotImplementedError("bipartite GATConv is not supported")
+        self._num_heads = num_heads
+        self._in_src_feats = self._in_dst_feats = in_feats
+        self._out_feats = out_feats
+        self._allow_zero_in_degree = allow_zero_in_degree
+        self.fc = nn.Linear(in_feats, out_feats * num_heads, bias=False)
+        self.attn_l = nn.Parameter(torch.FloatTensor(size=(1, num_heads, out_feats)))
+        self.attn_r = nn.Parameter(torch.FloatTensor(size=(1, num_heads, out_feats)))
+        self.feat_drop = nn.Dropout(feat_drop)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.leaky_relu = nn.LeakyReLU(negative_slope)
+        if bias:
+            self.bias = nn.Parameter(torch.FloatTensor(size=(num_heads * out_feats,)))
+        else:
+            self.register_buffer("bias", None)
+        if residual:
+            if in_feats != out_feats * num_heads:
+                self.res_fc = nn.Linear(in_feats, num_heads * out_feats, bias=False)
+            else:
+                self.res_fc = nn.Identity()
+        else:
+            self.register_buffer("res_fc", None)
+        self.reset_parameters()
+        self.activation = activation
+
+    def reset_parameters(self):
+        gain = nn.init.calculate_gain("relu")
+        nn.init.xavier_normal_(self.fc.weight, gain=gain)
+        nn.init.xavier_normal_(self.attn_l, gain=gain)
+        nn.init.xavier_normal_(self.attn_r, gain=gain)
+        if self.bias is not None:
+            nn.init.constant_(self.bias, 0)
+        if isinstance(self.res_fc, nn.Linear):
+            nn.init.xavier_normal_(self.res_fc.weight, gain=gain)
+
+    def set_allow_zero_in_degree(self, set_value):
+        self._allow_zero_in_degree = set_value
+
+    def forward(self, graph, feat, get_attention=False):
+        import dgl.function as fn
+        from dgl.ops import edge_softmax
+
+        _check_graph(graph)
+        if isinstance(feat, tuple):
+            raise NotImplementedError("bipartite input features are not supported")
+        with graph.local_scope():
+            if not self._allow_zero_in_degree and (graph._engine_graph().in_degrees() == 0).any():
+                raise plagnn.PlagnnError("There are 0-in-degree nodes in the graph; add self-loops "
+                                         "or set allow_zero_in_degree=True")
+            h = self.feat_drop(feat)
+            ft = self.fc(h).view(-1, self._num_heads, self._out_feats)
+            el = (ft * self.attn_l).sum(dim=-1).unsqueeze(-1)
+            er = (ft * self.attn_r).sum(dim=-1).unsqueeze(-1)
+            graph.srcdata.update({"ft": ft, "el": el})
+            graph.dstdata.update({"er": er})
+            graph.apply_edges(fn.u_add_v("el", "er", "e"))
+            e = self.leaky_relu(graph.edata.pop("e"))
+            graph.edata["a"] = self.attn_drop(edge_softmax(graph, e))
+            graph.update_all(fn.u_mul_e("ft", "a", "m"), fn.sum("m", "ft"))
+            rst = graph.dstdata["ft"]
+            if self.res_fc is not None:
+                rst = rst + self.res_fc(h).view(h.shape[0], -1, self._out_feats)
+            if self.bias is not None:
+                rst = rst + self.bias.view(1, self._num_heads, self._out_feats)
+            if self.activation:
+                rst = self.activation(rst)
+            if get_attention:
+                return rst, graph.edata["a"]
+            return rst
+
+
+__all__ = ["SAGEConv", "GraphConv", "GATConv"]

@@ -148,6 +148,10 @@ SIGNATURES = {
     "pg_spmm_sum_workspace": (_sz, [_csr, _i64]),
     "pg_spmm_sum": (_i, [_csr, _vp, _i64, _i64, _i, _vp, _vp, _i64, _vp, _sz, _vp]),
     "pg_sddmm_dot": (_i, [_csr, _vp, _i64, _vp, _i64, _i64, _i, _vp, _i64, _i, _vp, _vp]),
+    "pg_edge_softmax_fwd": (_i, [_csr, _vp, _i64, _i32, _vp, _i64, _vp]),
+    "pg_edge_softmax_bwd": (_i, [_csr, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp]),
+    "pg_spmm_sum_heads": (_i, [_csr, _vp, _i64, _i32, _vp, _i64, _i64, _vp, _i64, _vp, _sz, _vp]),
+    "pg_sddmm_dot_heads": (_i, [_csr, _vp, _i64, _vp, _i64, _i32, _i64, _vp, _i64, _vp]),
     "pg_argpos_to_src": (_i, [_csr, _vp, _i64, _i, _i64, _vp, _i64, _vp]),
     "pg_bias_act": (_i, [_vp, _i64, _i64, _i64, _vp, _i, _f, _vp]),
     "pg_act_bwd": (_i, [_vp, _i64, _vp, _i64, _i64, _i64, _i, _f, _vp]),
@@ -202,6 +206,10 @@ SIGNATURES = {
     "pg_spmm_sum_cpu": (_i, [_csr, _vp, _i64, _i64, _i, _vp, _vp, _i64]),
     "pg_argpos_to_src_cpu": (_i, [_csr, _vp, _i64, _i, _i64, _vp, _i64]),
     "pg_sddmm_dot_cpu": (_i, [_csr, _vp, _i64, _vp, _i64, _i64, _i, _vp, _i64, _i, _vp]),
+    "pg_edge_softmax_fwd_cpu": (_i, [_csr, _vp, _i64, _i32, _vp, _i64]),
+    "pg_edge_softmax_bwd_cpu": (_i, [_csr, _vp, _i64, _vp, _i64, _i32, _vp, _i64]),
+    "pg_spmm_sum_heads_cpu": (_i, [_csr, _vp, _i64, _i32, _vp, _i64, _i64, _vp, _i64]),
+    "pg_sddmm_dot_heads_cpu": (_i, [_csr, _vp, _i64, _vp, _i64, _i32, _i64, _vp, _i64]),
     "pg_last_error_string": (ctypes.c_char_p, []),
     "pg_version": (_i, []),
 }

@@ -196,9 +196,14 @@ class DeviceGraph:
         return self.device.type == "cuda"
 
     def edge_weight_slots(self, edge_weight: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-        """Edge weights given per edge id (DGL order) -> in-CSR slot order, f32 contiguous."""
+        """Edge weights given per edge id (DGL order) -> in-CSR slot order, f32 contiguous:
+        one weight per edge as a 1-D tensor, H > 1 weights per edge ((E, H, ...)) as (E, H)."""
         if edge_weight is None:
             return None
+        if edge_weight.dim() >= 2 and edge_weight.shape[0] == self.num_edges \
+                and edge_weight.numel() != self.num_edges:
+            w = edge_weight.reshape(self.num_edges, -1)
+            return w.to(device=self.device, dtype=torch.float32).index_select(0, self.eid).contiguous()
         w = edge_weight.reshape(-1)
         if w.numel() != self.num_edges:
             raise ValueError(f"edge_weight has {w.numel()} entries, graph has {self.num_edges} edges")

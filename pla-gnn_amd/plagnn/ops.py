@@ -192,6 +192,110 @@ def sddmm_dot(dg: DeviceGraph, D: torch.Tensor, X: torch.Tensor, mean: bool = Fa
     return de
 
 
+def _edge_heads(dg: DeviceGraph, name: str, *ts: torch.Tensor) -> int:
+    """The head count of (E, H) float32 edge tensors in slot order (one count for all)."""
+    H = ts[0].shape[1] if ts[0].dim() == 2 else -1
+    for t in ts:
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name}: float32 edge features expected")
+        if t.dim() != 2 or t.shape[0] != dg.num_edges or t.shape[1] != H:
+            raise ValueError(f"{name}: edge features {tuple(t.shape)} on a graph of {dg.num_edges} edges, "
+                             f"({dg.num_edges}, {H}) expected")
+    return H
+
+
+def edge_softmax(dg: DeviceGraph, scores: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Softmax of the (E, H) scores over the in-edges of each destination, per head, in
+    in-CSR slot order (pg_edge_softmax_fwd; dgl.ops.edge_softmax with norm_by='dst')."""
+    _check_device(dg, scores, out)
+    if out is None:
+        out = torch.empty(tuple(scores.shape), dtype=torch.float32, device=scores.device)
+    H = _edge_heads(dg, "edge_softmax", scores, out)
+    args = (dg.fwd.struct(None), ptr(scores), _ld(scores), H, ptr(out), _ld(out))
+    if dg.is_cuda:
+        call("pg_edge_softmax_fwd", *args, _stream(scores))
+    else:
+        call("pg_edge_softmax_fwd_cpu", *args)
+    return out
+
+
+def edge_softmax_backward(dg: DeviceGraph, a: torch.Tensor, da: torch.Tensor,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ds = a * (da - sum over the row of a * da) for a = edge_softmax(s) (pg_edge_softmax_bwd)."""
+    _check_device(dg, a, da, out)
+    if out is None:
+        out = torch.empty(tuple(a.shape), dtype=torch.float32, device=a.device)
+    H = _edge_heads(dg, "edge_softmax_backward", a, da, out)
+    args = (dg.fwd.struct(None), ptr(a), _ld(a), ptr(da), _ld(da), H, ptr(out), _ld(out))
+    if dg.is_cuda:
+        call("pg_edge_softmax_bwd", *args, _stream(a))
+    else:
+        call("pg_edge_softmax_bwd_cpu", *args)
+    return out
+
+
+def _head_width(name: str, X: torch.Tensor, n: int, H: int) -> int:
+    if X.dtype != torch.float32:
+        raise TypeError(f"{name}: float32 features expected")
+    if X.dim() != 2 or X.shape[0] != n or H < 1 or X.shape[1] % H != 0 or X.shape[1] == 0:
+        raise ValueError(f"{name}: features {tuple(X.shape)} do not split into {H} heads on {n} nodes")
+    return X.shape[1] // H
+
+
+def spmm_sum_heads(dg: DeviceGraph, A: torch.Tensor, X: torch.Tensor, H: int, transpose: bool = False,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[v, h*Fh + j] = sum over in-edges k of A[k, h] * X[src_k, h*Fh + j] with (E, H)
+    weights in slot order (pg_spmm_sum_heads; update_all(u_mul_e, sum) on (N, H, Fh) features).
+    transpose=True runs on the out-CSR: the feature gradient of the forward aggregation."""
+    _check_device(dg, A, X, out)
+    if _edge_heads(dg, "spmm_sum_heads", A) != H:
+        raise ValueError(f"spmm_sum_heads: weights {tuple(A.shape)} for {H} heads")
+    Fh = _head_width("spmm_sum_heads", X, dg.num_nodes, H)
+    if out is None:
+        out = torch.empty(dg.num_nodes, H * Fh, dtype=torch.float32, device=X.device)
+    g = (dg.bwd if transpose else dg.fwd).struct(None)
+    args = (g, ptr(A), _ld(A), H, ptr(X), _ld(X), Fh, ptr(out), _ld(out))
+    if dg.is_cuda:
+        ws_n = _lib.lib().pg_spmm_sum_workspace(g, H * Fh)
+        ws = _workspace(ws_n, X.device)
+        call("pg_spmm_sum_heads", *args, ptr(ws), ws_n, _stream(X))
+    else:
+        call("pg_spmm_sum_heads_cpu", *args)
+    return out
+
+
+def sddmm_dot_heads(dg: DeviceGraph, D: torch.Tensor, X: torch.Tensor, H: int,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Per-edge, per-head dot products de[k, h] = sum_j D[dst_k, h*Fh + j] * X[src_k, h*Fh + j],
+    (E, H) in slot order (pg_sddmm_dot_heads): the gradient of spmm_sum_heads w.r.t. its
+    weights (D = dout), and apply_edges(u_dot_v) on (N, H, Fh) operands."""
+    _check_device(dg, D, X, out)
+    Fh = _head_width("sddmm_dot_heads", D, dg.num_nodes, H)
+    if tuple(X.shape) != tuple(D.shape) or X.dtype != torch.float32:
+        raise ValueError(f"sddmm_dot_heads: operands {tuple(D.shape)}, {tuple(X.shape)}")
+    de = torch.empty(dg.num_edges, H, dtype=torch.float32, device=D.device) if out is None else out
+    if _edge_heads(dg, "sddmm_dot_heads", de) != H:
+        raise ValueError(f"sddmm_dot_heads: output {tuple(de.shape)} for {H} heads")
+    args = (dg.fwd.struct(None), ptr(D), _ld(D), ptr(X), _ld(X), H, Fh, ptr(de), max(_ld(de), H))
+    if dg.is_cuda:
+        call("pg_sddmm_dot_heads", *args, _stream(D))
+    else:
+        call("pg_sddmm_dot_heads_cpu", *args)
+    return de
+
+
+def segment_sum(dg: DeviceGraph, de_slots: torch.Tensor, transpose: bool = False) -> torch.Tensor:
+    """Sums of (E, T) edge values in slot order over the in-edges of each node (transpose: the
+    out-edges), (N, T): spmm_sum_heads with Fh = 1 and X = 1, at most 64 columns per call."""
+    E, T = de_slots.shape
+    out = torch.empty(dg.num_nodes, T, dtype=torch.float32, device=de_slots.device)
+    for c0 in range(0, T, 64):
+        Hc = min(64, T - c0)
+        ones = torch.ones(dg.num_nodes, Hc, dtype=torch.float32, device=de_slots.device)
+        spmm_sum_heads(dg, de_slots[:, c0:c0 + Hc], ones, Hc, transpose=transpose, out=out[:, c0:c0 + Hc])
+    return out
+
+
 def argpos_to_src(dg: DeviceGraph, argpos: torch.Tensor) -> torch.Tensor:
     """DGL's argX (int64 source ids; -1 where a row has no in-edge)."""
     n, F = argpos.shape
@@ -468,6 +572,89 @@ class EdgeDot(torch.autograd.Function):
         d_lhs = spmm_sum(ctx.dg, rhs, ew_slots=de, transpose=True) if ctx.needs_input_grad[0] else None
         d_rhs = spmm_sum(ctx.dg, lhs, ew_slots=de) if ctx.needs_input_grad[1] else None
         return d_lhs, d_rhs, None
+
+
+class EdgeSoftmax(torch.autograd.Function):
+    """edge_softmax over (E, H) scores in slot order; the backward is one
+    edge_softmax_backward call on the saved output."""
+
+    @staticmethod
+    def forward(ctx, scores_slots, dg):
+        a = edge_softmax(dg, scores_slots.contiguous())
+        ctx.dg = dg
+        ctx.save_for_backward(a)
+        return a
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, da):
+        (a,) = ctx.saved_tensors
+        return edge_softmax_backward(ctx.dg, a, da.contiguous()), None
+
+
+class SumAggregateHeads(torch.autograd.Function):
+    """update_all(u_mul_e, sum) on (N, H*Fh) features with (E, H) weights in slot order
+    (GATConv's aggregation): dX on the transposed CSR, dA as per-head dot products of dout and
+    X, each only when needed."""
+
+    @staticmethod
+    def forward(ctx, X, dg, A_slots, H):
+        X, A_slots = X.contiguous(), A_slots.contiguous()
+        ctx.dg, ctx.H = dg, H
+        ctx.save_for_backward(A_slots if ctx.needs_input_grad[0] else None,
+                              X if ctx.needs_input_grad[2] else None)
+        return spmm_sum_heads(dg, A_slots, X, H)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        A_slots, X = ctx.saved_tensors
+        dout = dout.contiguous()
+        dx = spmm_sum_heads(ctx.dg, A_slots, dout, ctx.H, transpose=True) if ctx.needs_input_grad[0] else None
+        dA = sddmm_dot_heads(ctx.dg, dout, X, ctx.H) if ctx.needs_input_grad[2] else None
+        return dx, None, dA, None
+
+
+class EdgeDotHeads(torch.autograd.Function):
+    """apply_edges(u_dot_v) on (N, H*Fh) operands: de[k, h] = <lhs[src_k, head h], rhs[dst_k,
+    head h]>, (E, H) in slot order; the input gradients are per-head weighted sums with the
+    incoming edge gradient as the weights (EdgeDot's backward, per head)."""
+
+    @staticmethod
+    def forward(ctx, lhs, rhs, dg, H):
+        lhs, rhs = lhs.contiguous(), rhs.contiguous()
+        ctx.dg, ctx.H = dg, H
+        ctx.save_for_backward(lhs, rhs)
+        return sddmm_dot_heads(dg, rhs, lhs, H)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, de):
+        lhs, rhs = ctx.saved_tensors
+        de = de.contiguous()
+        d_lhs = spmm_sum_heads(ctx.dg, de, rhs, ctx.H, transpose=True) if ctx.needs_input_grad[0] else None
+        d_rhs = spmm_sum_heads(ctx.dg, de, lhs, ctx.H) if ctx.needs_input_grad[1] else None
+        return d_lhs, d_rhs, None, None
+
+
+class EdgeAdd(torch.autograd.Function):
+    """apply_edges(u_add_v): out[e] = lhs[src_e] + rhs[dst_e] for (N, T) operands, (E, T) in
+    edge-id order. The forward is two gathers; the backward's segment sums over the in-edges
+    (d_rhs) and the out-edges (d_lhs) run on the engine in a fixed order (segment_sum), not
+    as an index_add_ over repeated indices."""
+
+    @staticmethod
+    def forward(ctx, lhs, rhs, dg, src, dst):
+        ctx.dg = dg
+        return lhs.index_select(0, src) + rhs.index_select(0, dst)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, de):
+        de_slots = de.index_select(0, ctx.dg.eid).contiguous()
+        d_lhs = segment_sum(ctx.dg, de_slots, transpose=True) if ctx.needs_input_grad[0] else None
+        d_rhs = segment_sum(ctx.dg, de_slots) if ctx.needs_input_grad[1] else None
+        return d_lhs, d_rhs, None, None, None
 
 
 def _padded(n: int, F: int, device) -> torch.Tensor:
