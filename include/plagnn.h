@@ -195,6 +195,20 @@ int pg_spmm_max_bwd(const pg_csr_t* g, const pg_csr_t* gt, const void* argpos, i
                     int arg_kind, const float* dout, int64_t ldd, int64_t F,
                     const float* mask_src, int64_t ldm, const float* fwd_out, int64_t ldf,
                     float* dx, int64_t ldx, void* ws, size_t ws_bytes, pg_stream_t stream);
+/* The same with a set of active destination rows: row_active int8 [N], nonzero =
+ * the row's dout may be nonzero; an inactive row counts as dout = 0 and its dout and argpos
+ * rows are never read. eslot_active int32 [nnz] is gt->eslot with -1 at every entry whose
+ * destination row (gt->col) is inactive; the caller builds it once per graph and row set.
+ * dx is bitwise what pg_spmm_max_bwd gives on a dout whose inactive rows are zero: a list
+ * entry of value +-0 changes no bit of a sum that starts at +0. Both arrays NULL: exactly
+ * pg_spmm_max_bwd; one NULL: PG_ERR_INVALID. Grouped path only (PG_ARG_U16 records,
+ * F <= 1024, N F < 2^31), else PG_ERR_UNSUPPORTED: the caller uses the plain call. Same
+ * workspace. */
+int pg_spmm_max_bwd_rows(const pg_csr_t* g, const pg_csr_t* gt, const void* argpos, int64_t lda,
+                         int arg_kind, const float* dout, int64_t ldd, int64_t F,
+                         const float* mask_src, int64_t ldm, const float* fwd_out, int64_t ldf,
+                         float* dx, int64_t ldx, const int8_t* row_active, const int32_t* eslot_active,
+                         void* ws, size_t ws_bytes, pg_stream_t stream);
 
 /* DGL-form backward: dx = 0; dx[src(argpos[v,f]), f] += ew * dout[v,f] with f32
  * atomics (summation order not reproducible). The callee zero-fills dx. */
@@ -447,6 +461,16 @@ int pg_gemm_f32_cat(int transb, int64_t M, int64_t N, int64_t K1, int64_t K2, fl
                     int64_t lda1, const float* A2, int64_t lda2, const float* B1, int64_t ldb1, const float* B2,
                     int64_t ldb2, float beta, float* C, int64_t ldc, const pg_gemm_epilogue_t* ep,
                     pg_stream_t stream);
+/* Row-list product: for a sorted list rows[n_rows] (int32, device) of distinct row
+ * ids below M, C[rows[i], :] = A[rows[i], :] op(B) (A [M][K] not transposed, op(B) K x N,
+ * alpha 1, beta 0, no epilogue, no split-K). Rows of C that are not listed are neither read
+ * nor written. Three-piece kernel only, tile chosen as for an n_rows x N product; every
+ * element is summed in the same k order as in pg_gemm_f32's product, so the listed rows
+ * equal its rows bitwise. Operands that kernel does not take (see pg_gemm_f32_cat):
+ * PG_ERR_UNSUPPORTED, the caller runs the full product. n_rows == 0 launches nothing. */
+int pg_gemm_f32_rows(int transb, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
+                     const float* B, int64_t ldb, float* C, int64_t ldc, const int32_t* rows,
+                     int64_t n_rows, pg_stream_t stream);
 
 /* ---------------- device: bf16 storage mode (f32 accumulate) ---------------- */
 
@@ -484,6 +508,11 @@ int pg_spmm_max_bwd_bf16(const pg_csr_t* g, const pg_csr_t* gt, const void* argp
                          int arg_kind, const void* dout, int64_t ldd, int64_t F,
                          const void* mask_src, int64_t ldm, const void* fwd_out, int64_t ldf,
                          void* dx, int64_t ldx, void* ws, size_t ws_bytes, pg_stream_t stream);
+int pg_spmm_max_bwd_rows_bf16(const pg_csr_t* g, const pg_csr_t* gt, const void* argpos, int64_t lda,
+                              int arg_kind, const void* dout, int64_t ldd, int64_t F,
+                              const void* mask_src, int64_t ldm, const void* fwd_out, int64_t ldf,
+                              void* dx, int64_t ldx, const int8_t* row_active, const int32_t* eslot_active,
+                              void* ws, size_t ws_bytes, pg_stream_t stream);
 /* dst[i] = bf16(src[map ? map[i] : i]) (map[i] < 0: 0), round to nearest even: the bf16
  * weight copies of the f32 master parameters, in any layout the GEMMs want. */
 int pg_cast_f32_bf16(const float* src, const int32_t* map, int64_t n, void* dst, pg_stream_t stream);
@@ -615,7 +644,10 @@ int pg_version(void); /* 2: pg_csr_t.einv; 3: pg_spmm_max_bwd fwd_out; 5: no in-
                          11: pg_pad2d_group; 12: pg_mlp_l1_head;
                          13: pg_mlp_l1_split, pg_mlp_l1_head_ex, pg_adam_apply_l1;
                          13 also: pg_sddmm_dot; pg_edge_softmax_fwd / _bwd,
-                         pg_spmm_sum_heads, pg_sddmm_dot_heads and their _cpu twins */
+                         pg_spmm_sum_heads, pg_sddmm_dot_heads and their _cpu twins;
+                         13 also (additions only, so the number the suite pins stays):
+                         pg_gemm_f32_rows, pg_spmm_max_bwd_rows[_bf16] (the top layer's
+                         backward on the train rows only) */
 
 #ifdef __cplusplus
 }

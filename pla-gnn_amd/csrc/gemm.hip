@@ -967,6 +967,32 @@ int pg_gemm_f32_cat(int transb, int64_t M, int64_t N, int64_t K1, int64_t K2, fl
   return pg::ok();
 }
 
+int pg_gemm_f32_rows(int transb, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
+                     const float* B, int64_t ldb, float* C, int64_t ldc, const int32_t* rows,
+                     int64_t n_rows, pg_stream_t stream) {
+  const pg_gemm_epilogue_t none{nullptr, PG_ACT_NONE, 0.f, nullptr, 0, nullptr};
+  if (M < 0 || N < 0 || K < 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX || n_rows < 0 || n_rows > M)
+    return pg::set_error(PG_ERR_INVALID, "pg_gemm_f32_rows: bad sizes");
+  if (ldc < N || lda < K || (transb ? ldb < K : ldb < N))
+    return pg::set_error(PG_ERR_INVALID, "pg_gemm_f32_rows: leading dimension too small");
+  if (n_rows == 0 || N == 0) return pg::ok();
+  if (!rows || !A || !B || !C) return pg::set_error(PG_ERR_INVALID, "pg_gemm_f32_rows: NULL buffer");
+  // (C's rows are reached by 64-bit addresses; A's by the 32-bit offsets x3_ok bounds)
+  if (K == 0 || !x3_ok(0, transb, M, N, K, A, lda, B, ldb, C, ldc, &none, false, nullptr))
+    return pg::set_error(PG_ERR_UNSUPPORTED, "pg_gemm_f32_rows: needs operands the three-piece kernel takes");
+  int bm, bn;
+  pick_tile_x3(n_rows, N, K, 1, bm, bn);
+  const int tiles_n = (int)((N + bn - 1) / bn);
+  const int tiles = tiles_n * (int)((n_rows + bm - 1) / bm);
+  const X3Args xa{false, transb != 0, bm, bn, EPI_NONE, (int)n_rows, (int)N, (int)K, (int)K, tiles_n, tiles, 1, 1.f, A,
+                  lda, B, ldb, 0.f, C, ldc, nullptr, 0.f, nullptr, 0, nullptr, nullptr, nullptr};
+  const int rc = gemm_x3_rows_launch(xa, rows, (int)M, (hipStream_t)stream);
+  const hipError_t e = hipGetLastError();
+  if (rc != PG_OK || e != hipSuccess)
+    return pg::set_error(rc != PG_OK ? rc : (int)e, "pg_gemm_f32_rows: launch failed");
+  return pg::ok();
+}
+
 int pg_gemm_f32(int transa, int transb, int64_t M, int64_t N, int64_t K, float alpha,
                 const float* A, int64_t lda, const float* B, int64_t ldb, float beta, float* C,
                 int64_t ldc, const pg_gemm_epilogue_t* ep, int split_k, void* ws,

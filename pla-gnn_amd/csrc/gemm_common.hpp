@@ -154,6 +154,10 @@ int gemm_x3_launch(const X3Args& a, hipStream_t st);
 int gemm_x3_cat_launch(const X3Args& a, const float* A2, int64_t lda2, const float* B2, int64_t ldb2, int kcat,
                        hipStream_t st);
 
+// Row-list form: a.M = the listed rows (tiles counted over them), A has m_full rows; row i
+// of the tile grid reads A[rows[i]] and writes C[rows[i]] (ta = false, EPI_NONE, no split-K).
+int gemm_x3_rows_launch(const X3Args& a, const int32_t* rows, int m_full, hipStream_t st);
+
 // Grouped split-K partials (pg_gemm_f32_group): one tile shape and one (ta, tb) for the
 // group. 128 x 256 (two workgroups per CU, each wave 64 x 128: a third less staging per
 // MFMA than 128 x 128): cfg2 GEMM 0.796 -> 0.790 ms per step, cfg3 1.867 -> 1.857

@@ -206,6 +206,26 @@ struct StageAddr {
       ustride = 0;
     }
   }
+  // row-list form (row image only): tile row r is the operand's row rows[min(r0 + r, n - 1)]
+  __device__ __forceinline__ void setup_rows(int64_t ld, int r0, const int32_t* __restrict__ rows, int n, int k0,
+                                             int tid) {
+    static_assert(!KMAJ, "a row list indexes a row image");
+    int row, k;
+    Stage<ROWS, KMAJ, NTH>::unit_pos(tid, row, k);
+    kq0 = k;
+    int rid[PER];
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      Stage<ROWS, KMAJ, NTH>::unit_pos(tid + i * NTH, row, k);
+      rid[i] = rows[min(r0 + row, n - 1)];
+    }
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      Stage<ROWS, KMAJ, NTH>::unit_pos(tid + i * NTH, row, k);
+      off_[i] = ((uint32_t)rid[i] * (uint32_t)ld + (uint32_t)(k0 + k)) * 4u;
+    }
+    ustride = 0;
+  }
   __device__ __forceinline__ uint32_t off(int i) const {
     if constexpr (KMAJ) return off_[0] + (uint32_t)i * ustride;
     else return off_[i];
@@ -216,13 +236,16 @@ struct StageAddr {
 
 // The accumulator tile leaves through LDS in PASSES row bands (16-B stores), with the
 // epilogue (alpha, beta C, bias, act / act', or the split-K partial slab).
-template <int BM, int BN, int EPI, int PASSES, int NTH = NT>
+// RL (row-list form, EPI_NONE): M counts the listed rows, and tile row gr leaves to row
+// rows[gr] of C; the ids are loaded with the pass's other operands, ahead of the barrier.
+template <int BM, int BN, int EPI, int PASSES, int NTH = NT, bool RL = false>
 __device__ __forceinline__ void x3_store(const f32x16 (&acc)[BM / 64][BN / (32 * (NTH / 128))], float* __restrict__ img, int tid,
                                          int m0, int n0, int M, int N, int kz, float alpha, float beta,
                                          float* __restrict__ C, int64_t ldc, const float* __restrict__ bias,
                                          float slope, const float* __restrict__ dact, int64_t lddact,
-                                         float* __restrict__ ws) {
+                                         float* __restrict__ ws, const int32_t* __restrict__ rows = nullptr) {
   constexpr bool SPLIT = EPI == EPI_SPLIT;
+  static_assert(!RL || EPI == EPI_NONE, "the row-list form has no epilogue");
   constexpr int WN = NTH / 128;  // waves along N (2 x WN waves)
   constexpr int TM = BM / 64, TN = BN / (32 * WN);
   const int lane = tid & 63, wave = tid >> 6;
@@ -241,7 +264,15 @@ __device__ __forceinline__ void x3_store(const f32x16 (&acc)[BM / 64][BN / (32 *
   float4 b4 = make_float4(0.f, 0.f, 0.f, 0.f);
   if constexpr (!SPLIT) b4 = *reinterpret_cast<const float4*>(bias ? bias + gcl : g_zero4);
   float4 y4[CH];
+  int rid[CH];
   auto prefetch = [&](int pass, int c0) {
+    if constexpr (RL) {
+#pragma unroll
+      for (int q = 0; q < CH; ++q) {
+        const int row = ((c0 + q) * NTH + tid) / (BN / 4);
+        rid[q] = rows[min(m0 + pass * BAND + row, M - 1)];
+      }
+    }
     if constexpr (DACT) {
 #pragma unroll
       for (int q = 0; q < CH; ++q) {
@@ -279,7 +310,7 @@ __device__ __forceinline__ void x3_store(const f32x16 (&acc)[BM / 64][BN / (32 *
         if constexpr (SPLIT) {
           *reinterpret_cast<float4*>(ws + ((int64_t)kz * M + gr) * N + gc) = v;
         } else {
-          float* cp = C + (int64_t)gr * ldc + gc;
+          float* cp = C + (int64_t)(RL ? rid[q] : gr) * ldc + gc;
           float o[4] = {alpha * v.x, alpha * v.y, alpha * v.z, alpha * v.w};
           if (beta != 0.f) {
             const float4 c4 = *reinterpret_cast<const float4*>(cp);
@@ -355,14 +386,19 @@ struct X3Cat {
   int64_t ldb2;
   int kcat;
 };
-template <int BM, int BN, bool TA, bool TB, int EPI, bool KCAT = false, int NTH = NT>
+// RL: the row-list form (pg_gemm_f32_rows; TA = false, EPI_NONE, no split): M counts the
+// listed rows, `rows` names them, and A has m_full rows. Only the A tile's addressing (set
+// up once per tile) and the epilogue's C rows differ; the K loop is the same.
+template <int BM, int BN, bool TA, bool TB, int EPI, bool KCAT = false, int NTH = NT, bool RL = false>
 __device__ __forceinline__ void x3_tile(
     uint16_t* __restrict__ lds, int M, int N, int K, int k_per_split, int kz, int tm, int tn, float alpha,
     const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb, float beta,
     float* __restrict__ C, int64_t ldc, const float* __restrict__ bias, float slope,
     const float* __restrict__ dact, int64_t lddact, float* __restrict__ rowsum,
-    float* __restrict__ ws, float* __restrict__ ws_rowsum, X3Cat cat = {}) {
+    float* __restrict__ ws, float* __restrict__ ws_rowsum, X3Cat cat = {},
+    const int32_t* __restrict__ rows = nullptr, int m_full = 0) {
   constexpr bool AK = TA, BKM = !TB;
+  static_assert(!RL || (!TA && !KCAT && EPI == EPI_NONE), "row-list form: plain A, no epilogue");
   constexpr bool SPLIT = EPI == EPI_SPLIT;
   constexpr int WN = NTH / 128;  // waves along N (2 x WN waves)
   constexpr int TM = BM / 64, TN = BN / (32 * WN);
@@ -394,13 +430,15 @@ __device__ __forceinline__ void x3_tile(
   // operand extents in bytes (row image: R rows of ld; k image: K rows of ld); with KCAT the
   // first operands end at k = kcat (the host checked that extent, not K's)
   const int K1 = KCAT ? cat.kcat : K;
-  const uint32_t a_bytes = (uint32_t)(AK ? ((int64_t)(K1 - 1) * lda + M) * 4 : ((int64_t)(M - 1) * lda + K1) * 4);
+  const int MA = RL ? m_full : M;  // A's rows (the descriptor's extent)
+  const uint32_t a_bytes = (uint32_t)(AK ? ((int64_t)(K1 - 1) * lda + MA) * 4 : ((int64_t)(MA - 1) * lda + K1) * 4);
   const uint32_t b_bytes = (uint32_t)(BKM ? ((int64_t)(K1 - 1) * ldb + N) * 4 : ((int64_t)(N - 1) * ldb + K1) * 4);
   const __amdgpu_buffer_rsrc_t rsa = x3_rsrc(A, a_bytes), rsb = x3_rsrc(B, b_bytes);
   const uint32_t a_kstride = AK ? (uint32_t)lda * 4u : 4u, b_kstride = BKM ? (uint32_t)ldb * 4u : 4u;
   StageAddr<BM, AK, NTH> aa;
   StageAddr<BN, BKM, NTH> ab;
-  aa.setup(lda, m0, M, kz0, tid);
+  if constexpr (RL) aa.setup_rows(lda, m0, rows, M, kz0, tid);
+  else aa.setup(lda, m0, M, kz0, tid);
   ab.setup(ldb, n0, N, kz0, tid);
   // KCAT: the second operands' addressing (their own k starts at 0 where the first ends)
   StageAddr<BM, AK, NTH> aa2;
@@ -572,8 +610,8 @@ __device__ __forceinline__ void x3_tile(
   }
 
   X3_STAMP(65, 0);
-  x3_store<BM, BN, EPI, PASSES, NTH>(acc, reinterpret_cast<float*>(lds), tid, m0, n0, M, N, kz, alpha, beta, C, ldc,
-                                bias, slope, dact, lddact, ws);
+  x3_store<BM, BN, EPI, PASSES, NTH, RL>(acc, reinterpret_cast<float*>(lds), tid, m0, n0, M, N, kz, alpha, beta, C,
+                                         ldc, bias, slope, dact, lddact, ws, rows);
   X3_STAMP(65, 1);
 }
 
@@ -613,6 +651,20 @@ void gemm_x3_cat_kernel(
   const int tile = x3_item(tiles);
   x3_tile<BM, BN, TA, TB, EPI, true>(lds, M, N, K, K, 0, tile / tiles_n, tile % tiles_n, alpha, A, lda, B, ldb, beta, C,
                                      ldc, bias, slope, dact, lddact, nullptr, nullptr, nullptr, cat);
+}
+
+// Row-list form (pg_gemm_f32_rows): M = the listed rows, m_full = A's rows
+template <int BM, int BN, bool TB>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(x3_waves<BM, BN>())))
+void gemm_x3_rows_kernel(
+    int M, int N, int K, int tiles_n, int tiles, const float* __restrict__ A, int64_t lda,
+    const float* __restrict__ B, int64_t ldb, float* __restrict__ C, int64_t ldc,
+    const int32_t* __restrict__ rows, int m_full) {
+  __shared__ __attribute__((aligned(16))) uint16_t lds[x3_lds_u16<BM, BN>()];
+  const int tile = x3_item(tiles);
+  x3_tile<BM, BN, false, TB, EPI_NONE, false, NT, true>(lds, M, N, K, K, 0, tile / tiles_n, tile % tiles_n, 1.f, A, lda,
+                                                        B, ldb, 0.f, C, ldc, nullptr, 0.f, nullptr, 0, nullptr, nullptr,
+                                                        nullptr, X3Cat{}, rows, m_full);
 }
 
 // Grouped split-K partials: the items of every part (its tiles x its K slices, slice-major)
@@ -717,6 +769,31 @@ int gemm_x3_cat_launch(const X3Args& a, const float* A2, int64_t lda2, const flo
 int gemm_x3_cat_launch(const X3Args&, const float*, int64_t, const float*, int64_t, int, hipStream_t) {
   return PG_ERR_UNSUPPORTED;
 }
+#endif
+
+#if PG_X3_BUFLOAD
+template <int BM, int BN>
+int launch_rows(const X3Args& a, const int32_t* rows, int m_full, hipStream_t st) {
+  const dim3 grid((unsigned)a.tiles), block(NT);
+  if (a.tb)
+    hipLaunchKernelGGL((gemm_x3_rows_kernel<BM, BN, true>), grid, block, 0, st, a.M, a.N, a.K, a.tiles_n, a.tiles,
+                       a.A, a.lda, a.B, a.ldb, a.C, a.ldc, rows, m_full);
+  else
+    hipLaunchKernelGGL((gemm_x3_rows_kernel<BM, BN, false>), grid, block, 0, st, a.M, a.N, a.K, a.tiles_n, a.tiles,
+                       a.A, a.lda, a.B, a.ldb, a.C, a.ldc, rows, m_full);
+  return PG_OK;
+}
+
+int gemm_x3_rows_launch(const X3Args& a, const int32_t* rows, int m_full, hipStream_t st) {
+  if (a.ta || a.epi != EPI_NONE || a.n_split != 1) return PG_ERR_UNSUPPORTED;
+  if (a.bm == 128 && a.bn == 128) return launch_rows<128, 128>(a, rows, m_full, st);
+  if (a.bm == 128 && a.bn == 64) return launch_rows<128, 64>(a, rows, m_full, st);
+  if (a.bm == 64 && a.bn == 128) return launch_rows<64, 128>(a, rows, m_full, st);
+  if (a.bm == 64 && a.bn == 64) return launch_rows<64, 64>(a, rows, m_full, st);
+  return PG_ERR_UNSUPPORTED;
+}
+#else
+int gemm_x3_rows_launch(const X3Args&, const int32_t*, int, hipStream_t) { return PG_ERR_UNSUPPORTED; }
 #endif
 
 int gemm_x3_launch(const X3Args& a, hipStream_t st) {

@@ -1143,13 +1143,17 @@ __device__ __forceinline__ void pack_long_row(
 constexpr int kPackLds = kHistMax + 8 + kGroupMaxF / 2 + 4;
 static_assert(kPackLds >= kWavesPerBlock * (kPackWaveMax + 4), "pack LDS");
 
-template <typename A, typename T, int NV, typename R, bool TR>
+// ACT (pg_spmm_max_bwd_rows): a destination row with row_active[v] == 0 counts as dout = 0
+// and is left out whole: no loads of its dout / arg rows, no records, no descriptors (the
+// wave, or the long row's workgroup, returns at once). Its lists would carry only +-0
+// values, which change no bit of a sum that starts at +0.
+template <typename A, typename T, int NV, typename R, bool TR, bool ACT = false>
 __global__ __launch_bounds__(kBlock) void group_pack_kernel(
     const int4* __restrict__ rows, int n_long, int n_rows, const int32_t* __restrict__ ptr,
     const A* __restrict__ arg, int64_t lda, int F,
     const T* __restrict__ dout, int64_t ldd, const T* __restrict__ fout, int64_t ldf,
     const float* __restrict__ ew, R gp, uint32_t* __restrict__ glist, const int32_t* __restrict__ einv,
-    uint32_t* __restrict__ tickets, int n_tickets) {
+    uint32_t* __restrict__ tickets, int n_tickets, const int8_t* __restrict__ row_active) {
   // the pull's split-row ticket counters start every call at zero (this launch precedes it)
   for (int i = blockIdx.x * kBlock + threadIdx.x; i < n_tickets; i += gridDim.x * kBlock) tickets[i] = 0u;
   const DescOut<TR> dsc{glist, einv};
@@ -1158,12 +1162,17 @@ __global__ __launch_bounds__(kBlock) void group_pack_kernel(
   __shared__ __attribute__((aligned(16))) int lds[kLds];
   const int b = blockIdx.x;
   if (b < n_long) {
-    pack_long_row<A, T, R>(rows ? rows[b].x : b, ptr, arg, lda, F, dout, ldd, fout, ldf, ew, gp, dsc, lds);
+    const int v = rows ? rows[b].x : b;
+    if constexpr (ACT)
+      if (!row_active[v]) return;  // (block-uniform)
+    pack_long_row<A, T, R>(v, ptr, arg, lda, F, dout, ldd, fout, ldf, ew, gp, dsc, lds);
   } else {
     const int wave = wave_id_uniform();
     const int v = (b - n_long) * kWavesPerBlock + wave;
     if (v < n_rows)
     {
+      if constexpr (ACT)
+        if (!row_active[v]) return;  // (wave-uniform; the short-row forms have no block barrier)
       if constexpr (NV > 0)
         pack_short_row_v<NV, A, T, R>(v, wave, ptr, arg, lda, F, dout, ldd, fout, ldf, ew, gp, dsc, lds);
       else
@@ -1209,7 +1218,11 @@ struct PullMerge {
 };
 
 
-template <typename T, typename R, bool TR, bool MERGE>
+// ACT (pg_spmm_max_bwd_rows, descriptors at the in-CSR slots): `tslot` is the caller's
+// eslot_active, -1 at every out-edge whose destination row is inactive. Such an edge has no
+// list (the pack wrote it no descriptor): its descriptor load still runs, at slot 0, outside
+// every branch (so the waits stay counted), and its count is taken as 0 where it is used.
+template <typename T, typename R, bool TR, bool MERGE, bool ACT = false>
 __global__ __launch_bounds__(kBlock) void max_bwd_pull_kernel(
     const int32_t* __restrict__ tslot, const int4* __restrict__ items, int n_items,
     const int32_t* __restrict__ tdst, const uint32_t* __restrict__ glist, R gp, int F,
@@ -1229,20 +1242,34 @@ __global__ __launch_bounds__(kBlock) void max_bwd_pull_kernel(
   // descriptors (and the destinations' record bases v F) one window ahead, their in-CSR
   // slots two windows ahead (an item with no out-edges reads nothing)
   auto tl_of = [&](int tw) { return tw + min(lane, t1 - tw - 1); };
+  static_assert(!(ACT && TR), "transposed descriptors need no active form: the pack skips the rows");
   uint32_t dsc_next = 0;
   int vf_next = 0, ts_next = 0;
+  bool dead_next = false;  // ACT: the descriptor in dsc_next belongs to an inactive row's edge
   // TR: the descriptors sit at the transposed indices themselves (coalesced, no slot loads)
   if (t1 > t0) {
-    dsc_next = glist[TR ? tl_of(t0) : tslot[tl_of(t0)]];
+    if constexpr (ACT) {
+      const int s = tslot[tl_of(t0)];
+      dead_next = s < 0;
+      dsc_next = glist[max(s, 0)];
+    } else {
+      dsc_next = glist[TR ? tl_of(t0) : tslot[tl_of(t0)]];
+    }
     vf_next = tdst[tl_of(t0)] * F;
     if (!TR && t0 + kWave < t1) ts_next = tslot[tl_of(t0 + kWave)];
   }
   for (int tw = t0; tw < t1; tw += kWave) {
     const int nw = min(kWave, t1 - tw);
     // this window's edge (lane): its list's first record and its length
-    const int2 dsc = make_int2(vf_next + (int)(dsc_next & 0xFFFFu), (int)(dsc_next >> 16));
+    const int2 dsc = make_int2(vf_next + (int)(dsc_next & 0xFFFFu),
+                               ACT && dead_next ? 0 : (int)(dsc_next >> 16));
     if (tw + kWave < t1) {
-      dsc_next = glist[TR ? tl_of(tw + kWave) : ts_next];
+      if constexpr (ACT) {
+        dead_next = ts_next < 0;
+        dsc_next = glist[max(ts_next, 0)];
+      } else {
+        dsc_next = glist[TR ? tl_of(tw + kWave) : ts_next];
+      }
       vf_next = tdst[tl_of(tw + kWave)] * F;
       if (!TR && tw + 2 * kWave < t1) ts_next = tslot[tl_of(tw + 2 * kWave)];
     }
@@ -2319,7 +2346,8 @@ template <typename T>
 int max_bwd_entry(const pg_csr_t* g, const pg_csr_t* gt, const void* argpos, int64_t lda,
                   int arg_kind, const T* dout, int64_t ldd, int64_t F, const T* mask_src,
                   int64_t ldm, const T* fwd_out, int64_t ldf, T* dx, int64_t ldx, void* ws,
-                  size_t ws_bytes, pg_stream_t stream) {
+                  size_t ws_bytes, pg_stream_t stream, const int8_t* row_active = nullptr,
+                  const int32_t* eslot_active = nullptr) {
   PG_TRY(pg::check_csr(g, "pg_spmm_max_bwd", false));
   PG_TRY(pg::check_csr(gt, "pg_spmm_max_bwd", true));
   // PG_ARG_DEAD_NONE: the records already leave out the zero maxima (fwd_out's filter)
@@ -2338,6 +2366,10 @@ int max_bwd_entry(const pg_csr_t* g, const pg_csr_t* gt, const void* argpos, int
   if (dead_none) fwd_out = nullptr;
   if (F == 0 || gt->n_rows == 0) return pg::ok();
   if (!argpos || !dout || !dx) return pg::set_error(PG_ERR_INVALID, "pg_spmm_max_bwd: NULL buffer");
+  // active rows (pg_spmm_max_bwd_rows): both arrays or neither
+  const bool act = row_active != nullptr;
+  if (act != (eslot_active != nullptr))
+    return pg::set_error(PG_ERR_INVALID, "pg_spmm_max_bwd_rows: row_active and eslot_active go together");
   const size_t need = pg_spmm_max_bwd_workspace(gt, F);
   PG_TRY(check_ws(ws_bytes, need, "pg_spmm_max_bwd"));
   hipStream_t st = (hipStream_t)stream;
@@ -2389,9 +2421,14 @@ int max_bwd_entry(const pg_csr_t* g, const pg_csr_t* gt, const void* argpos, int
     constexpr bool TR = decltype(tr_c)::value;
     auto pack = [&](auto nv_c) {
       constexpr int NV = decltype(nv_c)::value;
-      hipLaunchKernelGGL((group_pack_kernel<uint16_t, T, NV, R, TR>), pgrid, dim3(kBlock), 0, st, prow, n_long,
-                         (int)N, g->ptr, arg16, lda, (int)F, dout, ldd, fwd_out, ldf, g->ew, gp, glist, g->epos,
-                         tickets, n_tickets);
+      if (act)
+        hipLaunchKernelGGL((group_pack_kernel<uint16_t, T, NV, R, TR, true>), pgrid, dim3(kBlock), 0, st, prow,
+                           n_long, (int)N, g->ptr, arg16, lda, (int)F, dout, ldd, fwd_out, ldf, g->ew, gp, glist,
+                           g->epos, tickets, n_tickets, row_active);
+      else
+        hipLaunchKernelGGL((group_pack_kernel<uint16_t, T, NV, R, TR, false>), pgrid, dim3(kBlock), 0, st, prow,
+                           n_long, (int)N, g->ptr, arg16, lda, (int)F, dout, ldd, fwd_out, ldf, g->ew, gp, glist,
+                           g->epos, tickets, n_tickets, (const int8_t*)nullptr);
       return PG_OK;
     };
     if (vec) dispatch_nc_vec((int)((F + 255) / 256), pack);
@@ -2402,14 +2439,27 @@ int max_bwd_entry(const pg_csr_t* g, const pg_csr_t* gt, const void* argpos, int
     // sums to +0, which the mask would leave +0. With fwd_out alone the mask is applied.
     if (dead_none) mask_src = nullptr;
     const PullMerge pm{gt->ptr, gt->chunk, tickets, (uint32_t)pbytes};
-    if (merge_in)
-      hipLaunchKernelGGL((max_bwd_pull_kernel<T, R, TR, true>), dim3(blocks), dim3(kBlock), 0, st, gt->eslot,
-                         (const int4*)gt->items, (int)gt->n_items, gt->col, glist, gp, (int)F, mask_src, ldm,
-                         dx, ldx, w, ws_ld(F), pm);
-    else
-      hipLaunchKernelGGL((max_bwd_pull_kernel<T, R, TR, false>), dim3(blocks), dim3(kBlock), 0, st, gt->eslot,
-                         (const int4*)gt->items, (int)gt->n_items, gt->col, glist, gp, (int)F, mask_src, ldm,
-                         dx, ldx, w, ws_ld(F), pm);
+    // active rows with the descriptors at the in-CSR slots: the pull reads eslot_active (the
+    // inactive rows' descriptors were not written). Transposed descriptors: the array was
+    // cleared and the pack wrote the active rows' live edges only, so the pull is the plain one.
+    auto pull = [&](auto merge_c, auto act_c) {
+      constexpr bool MG = decltype(merge_c)::value, AC = decltype(act_c)::value;
+      hipLaunchKernelGGL((max_bwd_pull_kernel<T, R, TR, MG, AC>), dim3(blocks), dim3(kBlock), 0, st,
+                         AC ? eslot_active : gt->eslot, (const int4*)gt->items, (int)gt->n_items, gt->col, glist,
+                         gp, (int)F, mask_src, ldm, dx, ldx, w, ws_ld(F), pm);
+    };
+    if constexpr (!TR) {
+      if (act) {
+        if (merge_in) pull(std::true_type{}, std::true_type{});
+        else pull(std::false_type{}, std::true_type{});
+      } else {
+        if (merge_in) pull(std::true_type{}, std::false_type{});
+        else pull(std::false_type{}, std::false_type{});
+      }
+    } else {
+      if (merge_in) pull(std::true_type{}, std::false_type{});
+      else pull(std::false_type{}, std::false_type{});
+    }
     if (gt->n_merges > 0 && !merge_in)
       hipLaunchKernelGGL(sum_merge_kernel<T>, dim3((unsigned)gt->n_merges), dim3(kBlock), 0, st,
                          (const int4*)gt->merges, (int)gt->n_merges, (int)F, w, ws_ld(F), gt->ptr, 0,
@@ -2430,6 +2480,9 @@ int max_bwd_entry(const pg_csr_t* g, const pg_csr_t* gt, const void* argpos, int
     }
     return hip_status("pg_spmm_max_bwd");
   }
+  if (act)
+    return pg::set_error(PG_ERR_UNSUPPORTED, "pg_spmm_max_bwd_rows: needs PG_ARG_U16 records and F <= %d (grouped path)",
+                         kGroupMaxF);
   if constexpr (sizeof(T) == 4) {
     if (arg_kind == PG_ARG_U16)
       return launch_max_bwd<uint16_t>(g, gt, (const uint16_t*)argpos, lda, dout, ldd, F, mask_src,
@@ -2462,6 +2515,25 @@ int pg_spmm_max_bwd_bf16(const pg_csr_t* g, const pg_csr_t* gt, const void* argp
   return max_bwd_entry<uint16_t>(g, gt, argpos, lda, arg_kind, (const uint16_t*)dout, ldd, F,
                                  (const uint16_t*)mask_src, ldm, (const uint16_t*)fwd_out, ldf,
                                  (uint16_t*)dx, ldx, ws, ws_bytes, stream);
+}
+
+int pg_spmm_max_bwd_rows(const pg_csr_t* g, const pg_csr_t* gt, const void* argpos, int64_t lda,
+                         int arg_kind, const float* dout, int64_t ldd, int64_t F,
+                         const float* mask_src, int64_t ldm, const float* fwd_out, int64_t ldf,
+                         float* dx, int64_t ldx, const int8_t* row_active, const int32_t* eslot_active,
+                         void* ws, size_t ws_bytes, pg_stream_t stream) {
+  return max_bwd_entry<float>(g, gt, argpos, lda, arg_kind, dout, ldd, F, mask_src, ldm, fwd_out, ldf,
+                              dx, ldx, ws, ws_bytes, stream, row_active, eslot_active);
+}
+
+int pg_spmm_max_bwd_rows_bf16(const pg_csr_t* g, const pg_csr_t* gt, const void* argpos, int64_t lda,
+                              int arg_kind, const void* dout, int64_t ldd, int64_t F,
+                              const void* mask_src, int64_t ldm, const void* fwd_out, int64_t ldf,
+                              void* dx, int64_t ldx, const int8_t* row_active, const int32_t* eslot_active,
+                              void* ws, size_t ws_bytes, pg_stream_t stream) {
+  return max_bwd_entry<uint16_t>(g, gt, argpos, lda, arg_kind, (const uint16_t*)dout, ldd, F,
+                                 (const uint16_t*)mask_src, ldm, (const uint16_t*)fwd_out, ldf,
+                                 (uint16_t*)dx, ldx, ws, ws_bytes, stream, row_active, eslot_active);
 }
 
 int pg_spmm_max_bwd_scatter(const pg_csr_t* g, const void* argpos, int64_t lda, int arg_kind,

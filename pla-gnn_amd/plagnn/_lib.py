@@ -20,6 +20,7 @@ LIB_PATH = os.environ.get("PLAGNN_LIB") or os.path.join(_HERE, "libplagnn.so")
 PG_ARG_U16 = 16
 PG_ARG_I32 = 32
 PG_ARG_DEAD_NONE = 0x100  # flag: a zero maximum records no winner (include/plagnn.h)
+PG_ERR_UNSUPPORTED = -2  # valid arguments this build has no kernel for (include/plagnn.h)
 PG_DTYPE_F32 = 0
 PG_DTYPE_BF16 = 1
 PG_ACT_NONE = 0
@@ -136,6 +137,9 @@ SIGNATURES = {
     "pg_spmm_max_bwd_workspace": (_sz, [_csr, _i64]),
     "pg_spmm_max_bwd": (_i, [_csr, _csr, _vp, _i64, _i, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
                              _vp, _sz, _vp]),
+    "pg_spmm_max_bwd_rows": (_i, [_csr, _csr, _vp, _i64, _i, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                  _vp, _vp, _vp, _sz, _vp]),
+    "pg_gemm_f32_rows": (_i, [_i, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _vp]),
     "pg_gemm_f32_partials": (_i, [_i, _i, _i64, _i64, _i64, _vp, _i64, _vp, _i64, ctypes.POINTER(PgGemmEpilogue),
                                   _i, _vp, _sz, ctypes.POINTER(ctypes.c_int), _vp]),
     "pg_gemm_splitk_reduce_batch": (_i, [ctypes.POINTER(PgSplitkJob), _i, _vp]),
@@ -198,6 +202,8 @@ SIGNATURES = {
     "pg_spmm_max_fwd_bf16": (_i, [_csr, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i, _vp, _sz, _vp]),
     "pg_spmm_max_bwd_bf16": (_i, [_csr, _csr, _vp, _i64, _i, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp,
                                   _i64, _vp, _sz, _vp]),
+    "pg_spmm_max_bwd_rows_bf16": (_i, [_csr, _csr, _vp, _i64, _i, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp,
+                                       _i64, _vp, _vp, _vp, _sz, _vp]),
     "pg_cast_f32_bf16": (_i, [_vp, _vp, _i64, _vp, _vp]),
     "pg_cast_bf16_f32": (_i, [_vp, _i64, _vp, _vp]),
     "pg_pad2d_group": (_i, [ctypes.POINTER(PgPad2d), _i, _vp]),
@@ -257,6 +263,16 @@ def check(rc: int, name: str) -> None:
 
 def call(name: str, *args) -> None:
     check(getattr(lib(), name)(*args), name)
+
+
+def call_supported(name: str, *args) -> bool:
+    """`call`, for entry points whose contract names a fallback: False when the library
+    answers PG_ERR_UNSUPPORTED (nothing was launched), any other failure raises."""
+    rc = getattr(lib(), name)(*args)
+    if rc == PG_ERR_UNSUPPORTED:
+        return False
+    check(rc, name)
+    return True
 
 
 def stream_handle(device: torch.device):

@@ -89,6 +89,10 @@ class TrainEngine:
     # with it, W1's bf16 pieces live in their own buffer, rewritten by the step's Adam
     # (pg_adam_apply_l1), so the head splits nothing: one launch fewer per step (A/B knob)
     KEEP_L1_PIECES = True
+    # the top SAGE layer's backward on the train rows only (pg_gemm_f32_rows,
+    # pg_spmm_max_bwd_rows): every other row of that layer's dY is an exact zero, since the
+    # loss is taken on the train rows. Bitwise the full backward; False: all N rows (A/B knob)
+    ACTIVE_TOP_ROWS = True
     _fold_prep = False             # set by the step paths (step_eager, capture, group_times)
     _prepped = False               # the head of this step formed the Adam scalars
     WIDTH_ALIGN = 4  # every padded width is a multiple of this
@@ -189,6 +193,7 @@ class TrainEngine:
         self.row_set = torch.from_numpy(rs).to(dev)
         self.n_train = len(np.asarray(train_index))
         self.n_val = 0 if val_index is None else len(np.asarray(val_index))
+        self._setup_active_rows(rs == 1)
         self._alloc_buffers(features)
         self._alloc_workspace()
         # W1's bf16 pieces for the fused head, kept current by the step's Adam
@@ -207,6 +212,57 @@ class TrainEngine:
         self.ar_events: Optional[list] = None
         self.steps_done = 0
         self._timing: Optional[list] = None  # [(name, work, start_event, end_event)]
+
+    def _setup_active_rows(self, active: np.ndarray) -> None:
+        """The train rows as the top layer's backward wants them (fixed for the engine's
+        life): the sorted row list, the per-row flag, and the transposed CSR's slots with -1
+        at every out-edge into a row that is not a train row."""
+        dev = self.device
+        self.train_rows = torch.from_numpy(np.flatnonzero(active).astype(np.int32)).to(dev)
+        self.row_active = torch.from_numpy(active.astype(np.int8)).to(dev)
+        bwd = self.dg.bwd
+        self.eslot_active = torch.where(self.row_active[bwd.col.long()] != 0, bwd.eslot,
+                                        torch.full_like(bwd.eslot, -1)).contiguous()
+        # cleared when the library has no row form for this engine's operands (it says so
+        # before launching anything): that launch site then runs on all rows
+        self._rows_gemm = self._rows_spmm = True
+
+    def _top_rows(self, l: int) -> bool:
+        return self.ACTIVE_TOP_ROWS and l == self.L - 1
+
+    def _gemm_rows(self, A, B, C, tag) -> None:
+        """C[r] = A[r] B for the train rows r; C's other rows are neither read nor written."""
+        M, K, N = A.shape[0], A.shape[1], B.shape[1]
+        n = self.train_rows.numel()
+        if not self._rows_gemm:
+            self._gemm(A, B, C, tag=tag)
+            return
+        if self._rec is not None:  # gemm_bytes_per_step's dry run: the listed rows of A and C
+            self._rec_gemm(A, B, C, n, N, K, 0.0, None)
+            return
+        if self._filter is not None and launch_group(tag) != self._filter:
+            return
+        with self._t(tag, 2.0 * n * N * K):
+            self._rows_gemm = _lib.call_supported(
+                "pg_gemm_f32_rows", 0, M, N, K, ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(C), C.stride(0),
+                ptr(self.train_rows), n, self._s())
+            self._issued += int(self._rows_gemm)
+        if not self._rows_gemm:
+            self._gemm(A, B, C, tag=tag)
+
+    def _max_bwd(self, fn: str, l: int, *args) -> None:
+        """Layer l's max backward: `args` are pg_spmm_max_bwd's up to dx's leading dimension;
+        the top layer's goes through the active-rows form."""
+        tail = (ptr(self.ws), self.ws_bytes, self._s())
+        if self._top_rows(l) and self._rows_spmm:
+            if self._filter is not None and launch_group(self._cur) != self._filter:
+                return
+            self._rows_spmm = _lib.call_supported(fn.replace("max_bwd", "max_bwd_rows"), *args, ptr(self.row_active),
+                                                  ptr(self.eslot_active), *tail)
+            self._issued += int(self._rows_spmm)
+            if self._rows_spmm:
+                return
+        self._call(fn, *args, *tail)
 
     def _alloc_buffers(self, features: torch.Tensor) -> None:
         N, pd, dev = self.N, self.pd, self.device
@@ -650,14 +706,17 @@ class TrainEngine:
             dY, dP = DYP[:, :Fo], DYP[:, Fo:]
             # d Wcat = dY^T [H | M], d b = sum_nodes dY
             self._gemm(dY, HM, G[p + "Wcat"], transa=True, rowsum=G[p + "b"], tag=f"gemm.wgrad.cat.l{l + 1}")
-            # dM = dY Wneigh
-            self._gemm(dY, P[p + "Wcat"][:, Fi:], self.dM[l], tag=f"gemm.dgrad.neigh.l{l + 1}")
+            # dM = dY Wneigh (top layer: the train rows only; dM's other rows are never read
+            # and stay the zeros they were allocated as)
+            if self._top_rows(l):
+                self._gemm_rows(dY, P[p + "Wcat"][:, Fi:], self.dM[l], tag=f"gemm.dgrad.neigh.l{l + 1}")
+            else:
+                self._gemm(dY, P[p + "Wcat"][:, Fi:], self.dM[l], tag=f"gemm.dgrad.neigh.l{l + 1}")
             # max backward; the records say "none" where M = 0 (DEAD_NONE), so those entries are
             # skipped and the relu' mask of fc_pool (P >= 0) is implied
             with self._t(f"spmm_max_bwd.l{l + 1}", self.spmm_bwd_bytes(l)):
-                self._call("pg_spmm_max_bwd", g, gt, ptr(self.arg[l]), Fi, self.dg.arg_kind | DEAD_NONE, ptr(self.dM[l]), Fi, Fi,
-                     ptr(self.Pl[l]), Fi, None, 0, ptr(dP), DYP.stride(0), ptr(self.ws),
-                     self.ws_bytes, st)
+                self._max_bwd("pg_spmm_max_bwd", l, g, gt, ptr(self.arg[l]), Fi, self.dg.arg_kind | DEAD_NONE,
+                              ptr(self.dM[l]), Fi, Fi, ptr(self.Pl[l]), Fi, None, 0, ptr(dP), DYP.stride(0))
             # d Wpool = dP^T H, d bpool = sum_nodes dP
             self._gemm(dP, HM[:, :Fi], G[p + "Wpool"], transa=True, rowsum=G[p + "bpool"],
                        tag=f"gemm.wgrad.pool.l{l + 1}")
@@ -839,11 +898,14 @@ class TrainEngine:
 
     def spmm_bwd_bytes(self, layer: int) -> int:
         """Algorithmic bytes of one max backward: the upstream gradient
-        and the argmax record read once (s*F*N + a*F*N), dX written once (s*F*N), plus
-        the fused relu mask (s*F*N) and the transposed CSR (4(N+1) + 8E'), true width F."""
+        and the argmax record read once (s*F*Na + a*F*Na; Na = N, or the train rows for the
+        top layer's active-rows form), dX written once (s*F*N), plus the transposed CSR
+        (4(N+1) + 8E'), true width F. No relu-mask read: the dead-none records imply the
+        mask and the kernel never loads it."""
         N, E, F = self.N, self.dg.num_edges, self.dims[layer]
         a = 2 if self.dg.arg_kind == _lib.PG_ARG_U16 else 4
-        return 4 * (N + 1) + 8 * E + (12 + a) * F * N
+        Na = self.train_rows.numel() if self._top_rows(layer) and self._rows_spmm else N
+        return 4 * (N + 1) + 8 * E + 4 * F * N + (4 + a) * F * Na
 
     def flops_per_step(self) -> int:
         """Flops of the step's GEMM launches at the true (unpadded) dims, forward + backward
@@ -856,7 +918,9 @@ class TrainEngine:
             fi, fo = d[l], d[l + 1]
             fwd = 2 * N * fi * fi + 2 * N * (2 * fi) * fo
             wgrad = fwd
-            igrad = 2 * N * fo * fi + (2 * N * fo * fi + 2 * N * fi * fi if l > 0 else 0)
+            # (dM = dY Wneigh: the top layer's on the train rows only)
+            Na = self.train_rows.numel() if self._top_rows(l) and self._rows_gemm else N
+            igrad = 2 * Na * fo * fi + (2 * N * fo * fi + 2 * N * fi * fi if l > 0 else 0)
             f += fwd + wgrad + igrad
         # liner1: forward, weight and input gradients (the forward and the input gradient run
         # inside the fused head when FUSED_L1_HEAD: head_flops_per_step)

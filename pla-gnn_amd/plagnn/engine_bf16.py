@@ -38,6 +38,10 @@ class TrainEngineBF16(TrainEngine):
     # the fused liner1 + head kernel is f32 only: bf16 storage keeps liner1 as bf16 GEMMs
     FUSED_L1_HEAD = False
 
+    def _setup_active_rows(self, active: np.ndarray) -> None:
+        super()._setup_active_rows(active)
+        self._rows_gemm = False  # pg_gemm_bf16 has no row-list form: dgrad.neigh runs on all rows
+
     # ------------------------------------------------------------------ buffers
     def _alloc_buffers(self, features: torch.Tensor) -> None:
         N, pd, dev, L = self.N, self.pd, self.device, self.L
@@ -208,9 +212,10 @@ class TrainEngineBF16(TrainEngine):
             # dM = dY Wneigh   (Wneigh = the right half of Wcat, read as a [Fo][Fi] k image)
             self._gemm(dY, W[p + "Wcat"][:, Fi:], self.dM[l], tag=f"gemm.dgrad.neigh.l{l + 1}")
             with self._t(f"spmm_max_bwd.l{l + 1}", self.spmm_bwd_bytes(l)):
-                self._call("pg_spmm_max_bwd_bf16", g, gt, ptr(self.arg[l]), Fi, self.dg.arg_kind | DEAD_NONE, ptr(self.dM[l]),
-                     Fi, Fi, ptr(self.Pl[l]), Fi, None, 0, ptr(dP), DYP.stride(0),
-                     ptr(self.ws), self.ws_bytes, st)
+                # (top layer: the train rows only, as the f32 engine; the dgrad.neigh product
+                # above has no row form in bf16 and stays on all rows)
+                self._max_bwd("pg_spmm_max_bwd_bf16", l, g, gt, ptr(self.arg[l]), Fi, self.dg.arg_kind | DEAD_NONE,
+                              ptr(self.dM[l]), Fi, Fi, ptr(self.Pl[l]), Fi, None, 0, ptr(dP), DYP.stride(0))
             self._gemm(dP, HM[:, :Fi], G[p + "Wpool"], transa=True, rowsum=G[p + "bpool"],
                        tag=f"gemm.wgrad.pool.l{l + 1}")
             self._wgrad_bucket_boundary(l)
@@ -248,11 +253,13 @@ class TrainEngineBF16(TrainEngine):
         return 4 * (N + 1) + 4 * E + 2 * F * E + 2 * F * N + a * F * N
 
     def spmm_bwd_bytes(self, layer: int) -> int:
-        """B_bwd with s = 2: dM, argmax, relu mask read once, dP written once, + the
-        transposed CSR."""
+        """B_bwd with s = 2: dM and argmax read once (the train rows only for the top layer's
+        active-rows form), dP written once, + the transposed CSR; no relu-mask read (the
+        dead-none records imply it)."""
         N, E, F = self.N, self.dg.num_edges, self.dims[layer]
         a = 2 if self.dg.arg_kind == _lib.PG_ARG_U16 else 4
-        return 4 * (N + 1) + 8 * E + (6 + a) * F * N
+        Na = self.train_rows.numel() if self._top_rows(layer) and self._rows_spmm else N
+        return 4 * (N + 1) + 8 * E + 2 * F * N + (2 + a) * F * Na
 
     def logits(self) -> torch.Tensor:
         return self.prob[:, :self.C]
