@@ -27,6 +27,9 @@
  *                           weights (GATConv's aggregation) and its feature gradient
  *   pg_sddmm_dot_heads   <- its weight gradient; apply_edges(u_dot_v) on (N, H, Fh) operands.
  *                           Attention is not used by the reference: reference-unpinned.
+ *   pg_gspmm, pg_gsddmm  <- dgl.ops.gspmm / gsddmm: update_all and apply_edges with vector edge
+ *                           features ((E, F) beside (N, F)), every builtin binary message, copy_e,
+ *                           min; their backward. Not used by the reference: reference-unpinned.
  *   pg_argpos_to_src     <- DGL's argX (source node id of the max) from our compact
  *                           per-row edge positions
  *   pg_sigmoid_multi_loss<- th.sigmoid (code/model.py:29) + multi_loss
@@ -270,6 +273,49 @@ int pg_spmm_sum_heads(const pg_csr_t* g, const float* A, int64_t lda, int32_t H,
 int pg_sddmm_dot_heads(const pg_csr_t* g, const float* Dm, int64_t ldd, const float* X,
                        int64_t ldx, int32_t H, int64_t Fh, float* de, int64_t lde,
                        pg_stream_t stream);
+
+/* g-SpMM / g-SDDMM (DGL's gspmm / gsddmm): messages with vector edge features, f32.
+ * Binary operator of a message z = op(l, r), the reducer, and where an operand row of entry
+ * k of the CSR that is passed comes from: */
+#define PG_OP_ADD 0
+#define PG_OP_SUB 1
+#define PG_OP_MUL 2
+#define PG_OP_DIV 3      /* a true division (DGL multiplies by a reciprocal) */
+#define PG_OP_COPY_LHS 4 /* R is not read and may be NULL */
+#define PG_OP_COPY_RHS 5 /* L is not read and may be NULL */
+#define PG_RED_SUM 0
+#define PG_RED_MAX 1
+#define PG_RED_MIN 2
+#define PG_TGT_U 0 /* row col[k] */
+#define PG_TGT_V 1 /* the row that owns entry k (pg_gsddmm only) */
+#define PG_TGT_E 2 /* the edge row: eidx[k] if eidx != NULL, else g->eslot[k] if set, else k */
+
+/* out[v,f] = reduce_{k in row v} op(L[t_l(k), f], R[t_r(k), f]), lt, rt in {PG_TGT_U, PG_TGT_E}.
+ * On the transposed CSR the same call gives the source-side gradients. g->ew is not read.
+ * Sum: every schedule item sums in ascending k from +0, the pieces of a split row are added
+ *   in slot order from +0; norm_mode 1 divides a finished sum by the row's entry count
+ *   (rows without entries are not divided). argpos is not written.
+ * Max / min: pg_spmm_max_fwd's rules: strict compare, the first entry wins, pieces combined
+ *   in piece order (the earliest extremal entry wins); rows without entries give 0 and the
+ *   record "none"; a +-inf result is stored as 0; argpos (may be NULL) holds in-row positions,
+ *   u16 or i32 by arg_kind. norm_mode must be 0.
+ * No atomics, every out element is written, bitwise repeatable. The vector path (16-byte
+ * loads) needs F and every leading dimension a multiple of 4 and 16-byte aligned base
+ * pointers (8-byte for u16 records); anything else takes the scalar path. nnz == 0,
+ * n_rows == 0 and F == 0 succeed. Nothing is allocated or synchronised. */
+size_t pg_gspmm_workspace(const pg_csr_t* g, int64_t F, int reduce, int arg_kind);
+int pg_gspmm(const pg_csr_t* g, int op, int reduce, const float* L, int64_t ldl, int lt,
+             const float* R, int64_t ldr, int rt, const int32_t* eidx, int64_t F, int norm_mode,
+             float* out, int64_t ldo, void* argpos, int64_t lda, int arg_kind, void* ws,
+             size_t ws_bytes, pg_stream_t stream);
+/* out[e(k), f] = op(L[t_l(k), f], R[t_r(k), f]) for every entry k, targets in {U, V, E};
+ * e(k) is PG_TGT_E's row index, so with eidx a permutation every output row is written
+ * exactly once (out must not alias an operand). argpos != NULL: the masked form of the
+ * max / min backward: the value where argpos[v,f] == k - ptr[v], +0 elsewhere ("none"
+ * matches no edge). Every slot lies in exactly one schedule item: no workspace, no merge. */
+int pg_gsddmm(const pg_csr_t* g, int op, const float* L, int64_t ldl, int lt, const float* R,
+              int64_t ldr, int rt, const int32_t* eidx, int64_t F, float* out, int64_t ldo,
+              const void* argpos, int64_t lda, int arg_kind, pg_stream_t stream);
 
 /* argx[v,f] = col[ptr[v] + argpos[v,f]] (DGL's argX, int64), -1 where none. */
 int pg_argpos_to_src(const pg_csr_t* g, const void* argpos, int64_t lda, int arg_kind,
@@ -564,6 +610,14 @@ int pg_spmm_sum_heads_cpu(const pg_csr_t* g, const float* A, int64_t lda, int32_
                           const float* X, int64_t ldx, int64_t Fh, float* out, int64_t ldo);
 int pg_sddmm_dot_heads_cpu(const pg_csr_t* g, const float* Dm, int64_t ldd, const float* X,
                            int64_t ldx, int32_t H, int64_t Fh, float* de, int64_t lde);
+/* pg_gspmm / pg_gsddmm on host pointers: every row reduced in ascending k (a split row is
+ * not cut), OpenMP over rows; no work schedule, no workspace. */
+int pg_gspmm_cpu(const pg_csr_t* g, int op, int reduce, const float* L, int64_t ldl, int lt,
+                 const float* R, int64_t ldr, int rt, const int32_t* eidx, int64_t F,
+                 int norm_mode, float* out, int64_t ldo, void* argpos, int64_t lda, int arg_kind);
+int pg_gsddmm_cpu(const pg_csr_t* g, int op, const float* L, int64_t ldl, int lt, const float* R,
+                  int64_t ldr, int rt, const int32_t* eidx, int64_t F, float* out, int64_t ldo,
+                  const void* argpos, int64_t lda, int arg_kind);
 
 /* ---------------- device: §8f — edge clustering coefficient ---------------- */
 
@@ -647,7 +701,9 @@ int pg_version(void); /* 2: pg_csr_t.einv; 3: pg_spmm_max_bwd fwd_out; 5: no in-
                          pg_spmm_sum_heads, pg_sddmm_dot_heads and their _cpu twins;
                          13 also (additions only, so the number the suite pins stays):
                          pg_gemm_f32_rows, pg_spmm_max_bwd_rows[_bf16] (the top layer's
-                         backward on the train rows only) */
+                         backward on the train rows only);
+                         13 also: pg_gspmm, pg_gspmm_workspace, pg_gsddmm and their _cpu
+                         twins (vector edge features) */
 
 #ifdef __cplusplus
 }

@@ -82,6 +82,27 @@ inline int check_head_features(const char* who, int32_t H, int64_t Fh, std::init
   return PG_OK;
 }
 
+// pg_gspmm / pg_gsddmm [_cpu]: operator, targets (allow_v: pg_gsddmm), F and the leading
+// dimensions of the operands the operator reads, the record kind when records are passed
+inline bool gop_reads_lhs(int op) { return op != PG_OP_COPY_RHS; }
+inline bool gop_reads_rhs(int op) { return op != PG_OP_COPY_LHS; }
+inline int check_gop(const pg_csr_t* g, const char* who, int op, int64_t ldl, int lt, int64_t ldr,
+                     int rt, int64_t F, int64_t ldo, bool allow_v, const void* argpos, int64_t lda,
+                     int arg_kind) {
+  if (op < PG_OP_ADD || op > PG_OP_COPY_RHS) return set_error(PG_ERR_INVALID, "%s: bad op %d", who, op);
+  auto tgt_ok = [&](int t) { return t == PG_TGT_U || t == PG_TGT_E || (allow_v && t == PG_TGT_V); };
+  if ((gop_reads_lhs(op) && !tgt_ok(lt)) || (gop_reads_rhs(op) && !tgt_ok(rt)))
+    return set_error(PG_ERR_INVALID, "%s: bad operand target (%d, %d)", who, lt, rt);
+  if (F < 0 || ldo < F || (gop_reads_lhs(op) && ldl < F) || (gop_reads_rhs(op) && ldr < F) ||
+      (argpos && lda < F))
+    return set_error(PG_ERR_INVALID, "%s: bad F/leading dims", who);
+  if (F > (1 << 23)) return set_error(PG_ERR_UNSUPPORTED, "%s: F too large", who);
+  if (argpos && !valid_arg_kind(arg_kind)) return set_error(PG_ERR_INVALID, "%s: bad arg_kind %d", who, arg_kind);
+  if (argpos && arg_kind == PG_ARG_U16 && g->max_deg >= 0xFFFF)
+    return set_error(PG_ERR_INVALID, "%s: degree too large for u16 records", who);
+  return PG_OK;
+}
+
 }  // namespace pg
 
 #define PG_TRY(expr)           \

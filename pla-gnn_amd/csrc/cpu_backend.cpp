@@ -108,9 +108,122 @@ void sddmm_dot(const pg_csr_t* g, const float* D, int64_t ldd, const float* X, i
   }
 }
 
+inline float gop(int op, float l, float r) {
+  switch (op) {
+    case PG_OP_ADD: return l + r;
+    case PG_OP_SUB: return l - r;
+    case PG_OP_MUL: return l * r;
+    case PG_OP_DIV: return l / r;
+    case PG_OP_COPY_LHS: return l;
+    default: return r;
+  }
+}
+
+// operand row of entry k of row v: the gathered row, the owning row or the edge row
+inline const float* gop_row(const float* base, int64_t ld, int tgt, int32_t c, int64_t v, int32_t e) {
+  if (!base) return nullptr;
+  return base + (tgt == PG_TGT_U ? (int64_t)c : tgt == PG_TGT_V ? v : (int64_t)e) * ld;
+}
+
+inline void put_arg(void* arg, int arg_kind, int64_t i, int pos) {
+  if (arg_kind == PG_ARG_U16) ((uint16_t*)arg)[i] = (uint16_t)pos;
+  else ((int32_t*)arg)[i] = pos;
+}
+inline int get_arg(const void* arg, int arg_kind, int64_t i) {
+  if (arg_kind == PG_ARG_U16) {
+    const uint16_t a = ((const uint16_t*)arg)[i];
+    return a == 0xFFFF ? -1 : (int)a;
+  }
+  return ((const int32_t*)arg)[i];
+}
+
 }  // namespace
 
 extern "C" {
+
+int pg_gspmm_cpu(const pg_csr_t* g, int op, int reduce, const float* L, int64_t ldl, int lt,
+                 const float* R, int64_t ldr, int rt, const int32_t* eidx, int64_t F,
+                 int norm_mode, float* out, int64_t ldo, void* argpos, int64_t lda, int arg_kind) {
+  PG_TRY(pg::check_csr(g, "pg_gspmm_cpu", false));
+  if (reduce < PG_RED_SUM || reduce > PG_RED_MIN)
+    return pg::set_error(PG_ERR_INVALID, "pg_gspmm_cpu: bad reduce %d", reduce);
+  const bool sum = reduce == PG_RED_SUM;
+  if (sum) argpos = nullptr;
+  PG_TRY(pg::check_gop(g, "pg_gspmm_cpu", op, ldl, lt, ldr, rt, F, ldo, false, argpos, lda, arg_kind));
+  if (norm_mode < 0 || norm_mode > 1 || (norm_mode == 1 && !sum))
+    return pg::set_error(PG_ERR_INVALID, "pg_gspmm_cpu: bad norm_mode %d", norm_mode);
+  if (F == 0 || g->n_rows == 0) return pg::ok();
+  const bool ul = pg::gop_reads_lhs(op), ur = pg::gop_reads_rhs(op);
+  if (!out || (g->nnz > 0 && ((ul && !L) || (ur && !R))))
+    return pg::set_error(PG_ERR_INVALID, "pg_gspmm_cpu: NULL buffer");
+  if (!ul) L = nullptr;
+  if (!ur) R = nullptr;
+  const int32_t* emap = eidx ? eidx : g->eslot;
+  const float inf = std::numeric_limits<float>::infinity();
+  const float init = sum ? 0.f : (reduce == PG_RED_MIN ? inf : -inf);
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t v = 0; v < g->n_rows; ++v) {
+    float* o = out + v * ldo;
+    const int32_t b = g->ptr[v], e = g->ptr[v + 1];
+    for (int64_t f = 0; f < F; ++f) o[f] = init;
+    if (argpos)
+      for (int64_t f = 0; f < F; ++f) put_arg(argpos, arg_kind, v * lda + f, -1);
+    for (int32_t k = b; k < e; ++k) {
+      const int32_t ek = emap ? emap[k] : k;
+      const float* l = gop_row(L, ldl, lt, g->col[k], v, ek);
+      const float* r = gop_row(R, ldr, rt, g->col[k], v, ek);
+      for (int64_t f = 0; f < F; ++f) {
+        const float m = gop(op, l ? l[f] : 0.f, r ? r[f] : 0.f);
+        if (sum) {
+          o[f] += m;
+        } else if (reduce == PG_RED_MIN ? m < o[f] : m > o[f]) {
+          o[f] = m;
+          if (argpos) put_arg(argpos, arg_kind, v * lda + f, k - b);
+        }
+      }
+    }
+    if (sum) {
+      if (norm_mode == 1 && e > b) {
+        const float d = (float)(e - b);
+        for (int64_t f = 0; f < F; ++f) o[f] = o[f] / d;
+      }
+    } else {
+      for (int64_t f = 0; f < F; ++f)
+        if (std::isinf(o[f])) o[f] = 0.f;
+    }
+  }
+  return pg::ok();
+}
+
+int pg_gsddmm_cpu(const pg_csr_t* g, int op, const float* L, int64_t ldl, int lt, const float* R,
+                  int64_t ldr, int rt, const int32_t* eidx, int64_t F, float* out, int64_t ldo,
+                  const void* argpos, int64_t lda, int arg_kind) {
+  PG_TRY(pg::check_csr(g, "pg_gsddmm_cpu", false));
+  PG_TRY(pg::check_gop(g, "pg_gsddmm_cpu", op, ldl, lt, ldr, rt, F, ldo, true, argpos, lda, arg_kind));
+  if (F == 0 || g->n_rows == 0 || g->nnz == 0) return pg::ok();
+  const bool ul = pg::gop_reads_lhs(op), ur = pg::gop_reads_rhs(op);
+  if (!out || (ul && !L) || (ur && !R)) return pg::set_error(PG_ERR_INVALID, "pg_gsddmm_cpu: NULL buffer");
+  if ((ul && out == L) || (ur && out == R))
+    return pg::set_error(PG_ERR_INVALID, "pg_gsddmm_cpu: the output aliases an input");
+  if (!ul) L = nullptr;
+  if (!ur) R = nullptr;
+  const int32_t* emap = eidx ? eidx : g->eslot;
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t v = 0; v < g->n_rows; ++v) {
+    const int32_t b = g->ptr[v];
+    for (int32_t k = b; k < g->ptr[v + 1]; ++k) {
+      const int32_t ek = emap ? emap[k] : k;
+      const float* l = gop_row(L, ldl, lt, g->col[k], v, ek);
+      const float* r = gop_row(R, ldr, rt, g->col[k], v, ek);
+      float* o = out + (int64_t)ek * ldo;
+      for (int64_t f = 0; f < F; ++f) {
+        const bool take = !argpos || get_arg(argpos, arg_kind, v * lda + f) == k - b;
+        o[f] = take ? gop(op, l ? l[f] : 0.f, r ? r[f] : 0.f) : 0.f;
+      }
+    }
+  }
+  return pg::ok();
+}
 
 int pg_spmm_max_fwd_cpu(const pg_csr_t* g, const float* X, int64_t ldx, int64_t F, float* out,
                         int64_t ldo, void* argpos, int64_t lda, int arg_kind) {

@@ -17,7 +17,10 @@ SDDMM). Edge weights may require grad: every weighted aggregation is differentia
 respect to them, as DGL's GSpMM.backward is. Multi-head attention (reference-unpinned):
 ``apply_edges(u_add_v)``, ``dgl.ops.edge_softmax`` / ``dgl.nn.functional.edge_softmax``,
 ``u_dot_v`` and ``update_all(u_mul_e, sum)`` on (N, H, Fh) features with (E, H, 1) edge
-features, and ``dgl.nn.pytorch.GATConv`` built on them.
+features, and ``dgl.nn.pytorch.GATConv`` built on them. Vector edge features
+(reference-unpinned): every binary builtin ``{u,v,e}_{add,sub,mul,div,dot}_{u,v,e}``, ``copy_e``
+and the ``min`` reducer on node and edge features of equal trailing shapes, ``dgl.ops.gspmm`` /
+``gsddmm`` and ``dgl.nn.pytorch.EdgeConv`` (pg_gspmm, pg_gsddmm).
 
 Message passing on a CUDA (HIP) device always runs in libplagnn.so; a missing library is
 an error, never a silent fallback.
@@ -37,6 +40,7 @@ from . import nn  # noqa: F401  (dgl.nn)
 __version__ = "0.8.2+plagnn"
 
 _SEED: Optional[int] = None
+_BINARY_OPS = ("add", "sub", "mul", "div")
 
 
 def seed(val: int) -> None:
@@ -230,10 +234,17 @@ class DGLGraph:
 
         if not isinstance(message_func, _Message) or not isinstance(reduce_func, _Reduce):
             raise NotImplementedError("update_all supports dgl.function builtins only")
-        if message_func.op not in ("copy_u", "u_mul_e"):
+        parts = message_func.op.split("_")
+        binary = len(parts) == 3 and parts[1] in _BINARY_OPS and {parts[0], parts[2]} == {"u", "e"}
+        if message_func.op not in ("copy_u", "copy_e") and not binary:
             raise NotImplementedError(f"update_all: message function {message_func.op} is not supported")
         if reduce_func.msg != message_func.out:
             raise ValueError("reduce function reads a message the message function does not write")
+        if not self._scalar_edge_form(message_func, reduce_func):
+            self._update_all_gspmm(message_func, reduce_func)
+            if apply_node_func is not None:
+                self.ndata.update(apply_node_func(_NodeBatch(self)))
+            return
         X = self.ndata[message_func.lhs]
         ew = None
         if message_func.op == "u_mul_e":
@@ -258,6 +269,45 @@ class DGLGraph:
         self.ndata[reduce_func.out] = out
         if apply_node_func is not None:
             self.ndata.update(apply_node_func(_NodeBatch(self)))
+
+    def _scalar_edge_form(self, message_func, reduce_func) -> bool:
+        """True for the forms with at most one scalar per edge (or per head) that SAGEConv,
+        GraphConv and GATConv use: copy_u, and u_mul_e whose edge feature is not a vector of
+        the node feature's trailing shape, with sum / mean / max. They keep their entry points
+        (pg_spmm_sum, pg_spmm_max_fwd, pg_spmm_sum_heads); everything else is pg_gspmm."""
+        if reduce_func.op == "min" or message_func.op not in ("copy_u", "u_mul_e"):
+            return False
+        if message_func.op == "copy_u":
+            return True
+        X, ew = self.ndata[message_func.lhs], self.edata[message_func.rhs]
+        vector = ew.dim() >= 2 and ew.numel() != ew.shape[0] and X.shape[1:] == ew.shape[1:]
+        return not vector
+
+    def _field(self, target: str, name: str):
+        return self.edata[name] if target == "e" else self.ndata[name]
+
+    def _update_all_gspmm(self, message_func, reduce_func):
+        """update_all on pg_gspmm: copy_e, copy_u with min, and u_<op>_e / e_<op>_u with node and
+        edge features of equal trailing shapes (flattened to F), with sum / mean / max / min."""
+        op = message_func.op
+        if op == "copy_u":
+            kop, lt, rt, lhs, rhs = "copy_lhs", "u", "e", self.ndata[message_func.lhs], None
+        elif op == "copy_e":
+            kop, lt, rt, lhs, rhs = "copy_rhs", "u", "e", None, self.edata[message_func.lhs]
+        else:
+            lt, kop, rt = op.split("_")
+            lhs, rhs = self._field(lt, message_func.lhs), self._field(rt, message_func.rhs)
+            if lhs.shape[1:] != rhs.shape[1:]:
+                raise NotImplementedError(f"{op}: node and edge features of equal trailing shapes are supported, "
+                                          f"not {tuple(lhs.shape[1:])} with {tuple(rhs.shape[1:])}")
+        ref = lhs if lhs is not None else rhs
+        dg = self._device_graph(ref.device)
+
+        def flat(t):
+            return None if t is None else t.reshape(t.shape[0], -1).float()
+
+        out = _engine().ops.GSpMM.apply(dg, kop, reduce_func.op, flat(lhs), flat(rhs), lt, rt)
+        self.ndata[reduce_func.out] = out.to(ref.dtype).reshape((self._n,) + tuple(ref.shape[1:]))
 
     def _update_all_heads(self, X, ew, reduce_func):
         """update_all(u_mul_e, sum) with (N, H, Fh) features and (E, H, 1) weights, H > 1:
@@ -287,11 +337,18 @@ class DGLGraph:
         ndata[lhs][src_e] and ndata[rhs][dst_e] in edge-id order (DGL's SDDMM): shape (E, 1)
         for 2-D operands (pg_sddmm_dot), (E, H, 1) for (N, H, Fh) operands (pg_sddmm_dot_heads).
         apply_edges(dgl.function.u_add_v(lhs, rhs, out)): edata[out][e] = ndata[lhs][src_e] +
-        ndata[rhs][dst_e], any trailing shape."""
+        ndata[rhs][dst_e], any trailing shape. Every other binary builtin (two different
+        targets of u, v, e; add, sub, mul, div, dot): _apply_edges_gsddmm."""
         from .function import _Message
 
-        if not isinstance(func, _Message) or func.op not in ("u_dot_v", "u_add_v") or edges is not None:
-            raise NotImplementedError("apply_edges supports dgl.function.u_dot_v and u_add_v on all edges only")
+        parts = func.op.split("_") if isinstance(func, _Message) else ()
+        if len(parts) != 3 or parts[1] not in _BINARY_OPS + ("dot",) or parts[0] == parts[2] or edges is not None:
+            raise NotImplementedError("apply_edges supports the binary dgl.function builtins on all edges only")
+        if func.op not in ("u_dot_v", "v_dot_u", "u_add_v"):
+            self._apply_edges_gsddmm(func, *parts)
+            return
+        if func.op == "v_dot_u":  # the same dot product with the operands named the other way
+            func = _Message("u_dot_v", func.rhs, func.lhs, func.out)
         lhs, rhs = self.ndata[func.lhs], self.ndata[func.rhs]
         if lhs.shape != rhs.shape:
             raise ValueError(f"{func.op}: operand shapes {tuple(lhs.shape)} and {tuple(rhs.shape)} differ")
@@ -312,6 +369,22 @@ class DGLGraph:
         out = torch.empty_like(de).index_copy(0, dg.eid, de)
         shape = (-1, lhs.shape[1], 1) if lhs.dim() == 3 else (-1, 1)
         self.edata[func.out] = out.to(lhs.dtype).reshape(shape)
+
+    def _apply_edges_gsddmm(self, func, lt: str, op: str, rt: str):
+        """apply_edges on pg_gsddmm: edata[out][e] = op(lhs at lt, rhs at rt) for operands of
+        equal trailing shapes, in edge-id order; `dot` is the product summed over the last
+        dimension (keepdim)."""
+        lhs, rhs = self._field(lt, func.lhs), self._field(rt, func.rhs)
+        if lhs.shape[1:] != rhs.shape[1:]:
+            raise NotImplementedError(f"{func.op}: operands of equal trailing shapes are supported, "
+                                      f"not {tuple(lhs.shape[1:])} with {tuple(rhs.shape[1:])}")
+        dg = self._device_graph(lhs.device)
+        out = _engine().ops.GSDDMM.apply(dg, "mul" if op == "dot" else op, lhs.reshape(lhs.shape[0], -1).float(),
+                                         rhs.reshape(rhs.shape[0], -1).float(), lt, rt)
+        out = out.to(lhs.dtype).reshape((-1,) + tuple(lhs.shape[1:]))
+        if op == "dot":
+            out = out.sum(-1, keepdim=True) if out.dim() > 1 else out
+        self.edata[func.out] = out
 
     def __repr__(self):
         return (f"Graph(num_nodes={self._n}, num_edges={self.num_edges()},\n"

@@ -239,4 +239,47 @@ class GATConv(nn.Module):
             return rst
 
 
-__all__ = ["SAGEConv", "GraphConv", "GATConv"]
+class EdgeConv(nn.Module):
+    """DGL 0.8.2 ``EdgeConv(in_feat, out_feat, batch_norm=False, allow_zero_in_degree=False)``
+    (Wang et al., Dynamic Graph CNN): h_v = max over in-edges (u -> v) of
+    theta(h_v - h_u) + phi(h_v) (v_sub_u, as DGL's code has it), written on the shim's own primitives (vector edge features on
+    pg_gsddmm / pg_gspmm): apply_edges(v_sub_u), theta on the edge tensor, apply_edges(e_add_v),
+    optionally batch norm over the edges, update_all(copy_e, max). Parameters are named as
+    DGL's (theta, phi, bn). Not used by the reference: reference-unpinned."""
+
+    def __init__(self, in_feat, out_feat, batch_norm=False, allow_zero_in_degree=False):
+        super().__init__()
+        if isinstance(in_feat, tuple):
+            raise NotImplementedError("bipartite input features are not supported")
+        self.batch_norm = batch_norm
+        self._allow_zero_in_degree = allow_zero_in_degree
+        self.theta = nn.Linear(in_feat, out_feat)
+        self.phi = nn.Linear(in_feat, out_feat)
+        if batch_norm:
+            self.bn = nn.BatchNorm1d(out_feat)
+
+    def set_allow_zero_in_degree(self, set_value):
+        self._allow_zero_in_degree = set_value
+
+    def forward(self, g, feat):
+        import dgl.function as fn
+
+        _check_graph(g)
+        if isinstance(feat, tuple):
+            raise NotImplementedError("bipartite input features are not supported")
+        with g.local_scope():
+            if not self._allow_zero_in_degree and (g._engine_graph().in_degrees() == 0).any():
+                raise plagnn.PlagnnError("There are 0-in-degree nodes in the graph; add self-loops "
+                                         "or set allow_zero_in_degree=True")
+            g.srcdata["x"] = feat
+            g.apply_edges(fn.v_sub_u("x", "x", "theta"))
+            g.edata["theta"] = self.theta(g.edata["theta"])
+            g.dstdata["phi"] = self.phi(feat)
+            g.apply_edges(fn.e_add_v("theta", "phi", "e"))
+            if self.batch_norm:
+                g.edata["e"] = self.bn(g.edata["e"])
+            g.update_all(fn.copy_e("e", "e"), fn.max("e", "x"))
+            return g.dstdata["x"]
+
+
+__all__ = ["SAGEConv", "GraphConv", "GATConv", "EdgeConv"]

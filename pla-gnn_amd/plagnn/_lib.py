@@ -21,6 +21,10 @@ PG_ARG_U16 = 16
 PG_ARG_I32 = 32
 PG_ARG_DEAD_NONE = 0x100  # flag: a zero maximum records no winner (include/plagnn.h)
 PG_ERR_UNSUPPORTED = -2  # valid arguments this build has no kernel for (include/plagnn.h)
+# pg_gspmm / pg_gsddmm: operators, reducers, operand targets (include/plagnn.h)
+PG_OP = {"add": 0, "sub": 1, "mul": 2, "div": 3, "copy_lhs": 4, "copy_rhs": 5}
+PG_RED = {"sum": 0, "max": 1, "min": 2}
+PG_TGT = {"u": 0, "v": 1, "e": 2}
 PG_DTYPE_F32 = 0
 PG_DTYPE_BF16 = 1
 PG_ACT_NONE = 0
@@ -216,6 +220,12 @@ SIGNATURES = {
     "pg_edge_softmax_bwd_cpu": (_i, [_csr, _vp, _i64, _vp, _i64, _i32, _vp, _i64]),
     "pg_spmm_sum_heads_cpu": (_i, [_csr, _vp, _i64, _i32, _vp, _i64, _i64, _vp, _i64]),
     "pg_sddmm_dot_heads_cpu": (_i, [_csr, _vp, _i64, _vp, _i64, _i32, _i64, _vp, _i64]),
+    "pg_gspmm_workspace": (_sz, [_csr, _i64, _i, _i]),
+    "pg_gspmm": (_i, [_csr, _i, _i, _vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _vp, _i64, _i,
+                      _vp, _sz, _vp]),
+    "pg_gsddmm": (_i, [_csr, _i, _vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp]),
+    "pg_gspmm_cpu": (_i, [_csr, _i, _i, _vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _vp, _i64, _i]),
+    "pg_gsddmm_cpu": (_i, [_csr, _i, _vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i]),
     "pg_last_error_string": (ctypes.c_char_p, []),
     "pg_version": (_i, []),
 }

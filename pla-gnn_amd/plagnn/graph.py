@@ -195,6 +195,16 @@ class DeviceGraph:
     def is_cuda(self) -> bool:
         return self.device.type == "cuda"
 
+    def edge_map(self, transpose: bool = False) -> torch.Tensor:
+        """int32 edge id of every entry of the in-CSR (transpose: of the out-CSR, eid[eslot]):
+        pg_gspmm / pg_gsddmm's `eidx`, with which edge tensors are read and written in edge-id
+        order. Built once per device graph."""
+        maps = self.__dict__.setdefault("_edge_maps", {})
+        if transpose not in maps:
+            eid = self.eid.to(torch.int32)
+            maps[transpose] = eid[self.bwd.eslot.long()].contiguous() if transpose else eid.contiguous()
+        return maps[transpose]
+
     def edge_weight_slots(self, edge_weight: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         """Edge weights given per edge id (DGL order) -> in-CSR slot order, f32 contiguous:
         one weight per edge as a 1-D tensor, H > 1 weights per edge ((E, H, ...)) as (E, H)."""

@@ -284,6 +284,133 @@ def sddmm_dot_heads(dg: DeviceGraph, D: torch.Tensor, X: torch.Tensor, H: int,
     return de
 
 
+def _gop_args(dg: DeviceGraph, name: str, op: str, lhs, rhs, lhs_target: str, rhs_target: str, targets: str):
+    """Checked operands of gspmm / gsddmm: (op code, lhs, rhs, F); an operand the operator
+    does not read becomes None."""
+    if op not in _lib.PG_OP:
+        raise ValueError(f"{name}: unknown operator {op!r}")
+    if op == "copy_rhs":
+        lhs = None
+    if op == "copy_lhs":
+        rhs = None
+    F = None
+    for t, tgt, side in ((lhs, lhs_target, "lhs"), (rhs, rhs_target, "rhs")):
+        if t is None:
+            if (side == "lhs") != (op == "copy_rhs"):
+                raise ValueError(f"{name}: {op} needs its {side} operand")
+            continue
+        if tgt not in targets:
+            raise ValueError(f"{name}: {side} target {tgt!r}, one of {tuple(targets)} expected")
+        rows = dg.num_edges if tgt == "e" else dg.num_nodes
+        if t.dtype != torch.float32:
+            raise TypeError(f"{name}: float32 operands expected")
+        if t.dim() != 2 or t.shape[0] != rows or (F is not None and t.shape[1] != F):
+            raise ValueError(f"{name}: {side} operand {tuple(t.shape)} at target {tgt!r} on a graph of "
+                             f"{dg.num_nodes} nodes and {dg.num_edges} edges")
+        F = t.shape[1]
+    _check_device(dg, lhs, rhs)
+    return _lib.PG_OP[op], lhs, rhs, F
+
+
+def _edge_index(dg: DeviceGraph, eidx, transpose: bool) -> Optional[torch.Tensor]:
+    """`eidx` of pg_gspmm / pg_gsddmm: "eid" = edge tensors in edge-id order (the cached map),
+    None = in-CSR slot order, or an int32 tensor with one edge row index per CSR entry."""
+    if isinstance(eidx, str):
+        if eidx != "eid":
+            raise ValueError(f"eidx: 'eid', None or an int32 tensor expected, not {eidx!r}")
+        return dg.edge_map(transpose)
+    if eidx is not None and (eidx.dtype != torch.int32 or eidx.numel() != dg.num_edges
+                             or eidx.device != dg.device or not eidx.is_contiguous()):
+        raise ValueError("eidx: a contiguous int32 tensor with one entry per edge on the graph's device expected")
+    return eidx
+
+
+def _arg_kind(csr, arg_kind: Optional[int]) -> int:
+    if arg_kind is None:
+        arg_kind = _lib.PG_ARG_U16 if csr.max_deg < 0xFFFF else _lib.PG_ARG_I32
+    if arg_kind not in (_lib.PG_ARG_U16, _lib.PG_ARG_I32):
+        raise ValueError(f"arg_kind {arg_kind}")
+    return arg_kind
+
+
+def _arg_dtype(arg_kind: int):
+    return torch.int16 if arg_kind == _lib.PG_ARG_U16 else torch.int32
+
+
+def gspmm(dg: DeviceGraph, op: str, reduce: str, lhs: Optional[torch.Tensor], rhs: Optional[torch.Tensor],
+          lhs_target: str = "u", rhs_target: str = "e", transpose: bool = False, eidx="eid",
+          out: Optional[torch.Tensor] = None, argpos: Optional[torch.Tensor] = None,
+          arg_kind: Optional[int] = None, want_arg: bool = True):
+    """out[v] = reduce over the in-edges k of v of op(lhs[t_l(k)], rhs[t_r(k)]) (pg_gspmm): op
+    in add / sub / mul / div / copy_lhs / copy_rhs, reduce in sum / mean / max / min, targets
+    'u' (the source row) or 'e' (the edge row; `eidx`: see _edge_index). transpose=True runs on
+    the out-CSR, where 'u' is the destination of each out-edge: the source-side gradients.
+    Returns out for sum / mean, (out, argpos) for max / min (argpos None with want_arg=False)."""
+    name = "gspmm"
+    code, lhs, rhs, F = _gop_args(dg, name, op, lhs, rhs, lhs_target, rhs_target, "ue")
+    if reduce not in ("sum", "mean", "max", "min"):
+        raise ValueError(f"{name}: unknown reducer {reduce!r}")
+    red = _lib.PG_RED["sum" if reduce == "mean" else reduce]
+    csr = dg.bwd if transpose else dg.fwd
+    g = csr.struct(None)
+    emap = _edge_index(dg, eidx, transpose)
+    n = dg.num_nodes
+    dev = (lhs if lhs is not None else rhs).device
+    if out is None:
+        out = torch.empty(n, F, dtype=torch.float32, device=dev)
+    cmp_ = reduce in ("max", "min")
+    kind = _arg_kind(csr, arg_kind)
+    if cmp_ and want_arg and argpos is None:
+        argpos = torch.empty(n, F, dtype=_arg_dtype(kind), device=dev)
+    if not cmp_:
+        argpos = None
+    _check_device(dg, out, argpos)
+    if tuple(out.shape) != (n, F) or (argpos is not None and (tuple(argpos.shape) != (n, F)
+                                                             or argpos.dtype != _arg_dtype(kind))):
+        raise ValueError(f"{name}: output buffers do not match ({n}, {F}) / the record kind")
+    args = (g, code, red, ptr(lhs), _ld(lhs) if lhs is not None else 0, _lib.PG_TGT[lhs_target],
+            ptr(rhs), _ld(rhs) if rhs is not None else 0, _lib.PG_TGT[rhs_target], ptr(emap), F,
+            int(reduce == "mean"), ptr(out), _ld(out), ptr(argpos), _ld(argpos) if argpos is not None else 0, kind)
+    if dg.is_cuda:
+        ws_n = _lib.lib().pg_gspmm_workspace(g, F, red, kind)
+        ws = _workspace(ws_n, dev)
+        call("pg_gspmm", *args, ptr(ws), ws_n, _stream(out))
+    else:
+        call("pg_gspmm_cpu", *args)
+    return (out, argpos) if cmp_ else out
+
+
+def gsddmm(dg: DeviceGraph, op: str, lhs: Optional[torch.Tensor], rhs: Optional[torch.Tensor],
+           lhs_target: str = "u", rhs_target: str = "v", transpose: bool = False, eidx="eid",
+           out: Optional[torch.Tensor] = None, argpos: Optional[torch.Tensor] = None,
+           arg_kind: Optional[int] = None) -> torch.Tensor:
+    """out[e] = op(lhs[t_l(e)], rhs[t_r(e)]) per edge (pg_gsddmm), (E, F) in the order `eidx`
+    gives ("eid": edge-id order); targets 'u' (source), 'v' (destination), 'e'. With `argpos`
+    (a max / min reduce's records) the value only where the edge won, +0 elsewhere."""
+    name = "gsddmm"
+    code, lhs, rhs, F = _gop_args(dg, name, op, lhs, rhs, lhs_target, rhs_target, "uve")
+    csr = dg.bwd if transpose else dg.fwd
+    emap = _edge_index(dg, eidx, transpose)
+    dev = (lhs if lhs is not None else rhs).device
+    if out is None:
+        out = torch.empty(dg.num_edges, F, dtype=torch.float32, device=dev)
+    kind = _arg_kind(csr, arg_kind)
+    _check_device(dg, out, argpos)
+    if tuple(out.shape) != (dg.num_edges, F) or out.dtype != torch.float32:
+        raise ValueError(f"{name}: output {tuple(out.shape)}, ({dg.num_edges}, {F}) float32 expected")
+    if argpos is not None and (tuple(argpos.shape) != (dg.num_nodes, F) or argpos.dtype != _arg_dtype(kind)):
+        raise ValueError(f"{name}: argpos does not match ({dg.num_nodes}, {F}) / the record kind")
+    args = (csr.struct(None), code, ptr(lhs), _ld(lhs) if lhs is not None else 0, _lib.PG_TGT[lhs_target],
+            ptr(rhs), _ld(rhs) if rhs is not None else 0, _lib.PG_TGT[rhs_target], ptr(emap), F,
+            ptr(out), _ld(out) if out.numel() else max(F, 1), ptr(argpos),
+            _ld(argpos) if argpos is not None else 0, kind)
+    if dg.is_cuda:
+        call("pg_gsddmm", *args, _stream(out))
+    else:
+        call("pg_gsddmm_cpu", *args)
+    return out
+
+
 def segment_sum(dg: DeviceGraph, de_slots: torch.Tensor, transpose: bool = False) -> torch.Tensor:
     """Sums of (E, T) edge values in slot order over the in-edges of each node (transpose: the
     out-edges), (N, T): spmm_sum_heads with Fh = 1 and X = 1, at most 64 columns per call."""
@@ -655,6 +782,139 @@ class EdgeAdd(torch.autograd.Function):
         d_lhs = segment_sum(ctx.dg, de_slots, transpose=True) if ctx.needs_input_grad[0] else None
         d_rhs = segment_sum(ctx.dg, de_slots) if ctx.needs_input_grad[1] else None
         return d_lhs, d_rhs, None, None, None
+
+
+def _local_grad(op: str, side: str):
+    """(kind, sign) of dz/dx for z = op(lhs, rhs) and x the operand on `side`, y its partner:
+    'one' (sign), 'partner' (y), 'inv' (1 / y), 'den' (-y / x^2); None: z does not depend on x."""
+    if op == "add":
+        return "one", 1.0
+    if op == "sub":
+        return "one", 1.0 if side == "lhs" else -1.0
+    if op == "mul":
+        return "partner", 1.0
+    if op == "div":
+        return ("inv", 1.0) if side == "lhs" else ("den", 1.0)
+    if (op, side) in (("copy_lhs", "lhs"), ("copy_rhs", "rhs")):
+        return "one", 1.0
+    return None
+
+
+def _finish_grad(kind: str, sign: float, s: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    if kind == "den":
+        return -s / (x * x)
+    return s if sign == 1.0 else -s
+
+
+def _edge_term(dg, kind: str, d, d_target: str, y, y_target: str, argpos=None, arg_kind=None):
+    """(E, F) in edge-id order: d[t_d(e)] times the partner factor of `kind` (without a 'den'
+    operand's own -1 / x^2), through pg_gsddmm; masked by `argpos` when given."""
+    if kind == "one":
+        return gsddmm(dg, "copy_lhs", d, None, d_target, "e", argpos=argpos, arg_kind=arg_kind)
+    return gsddmm(dg, "div" if kind == "inv" else "mul", d, y, d_target, y_target, argpos=argpos,
+                  arg_kind=arg_kind)
+
+
+class GSpMM(torch.autograd.Function):
+    """out[v] = reduce over in-edges of op(lhs, rhs) with one operand at 'u' ((N, F)) and one at
+    'e' ((E, F), edge-id order), or a copy of either (pg_gspmm). Backward, only where needed:
+    sum / mean: a 'u' operand's gradient is pg_gspmm on the transposed CSR with dout as the
+    gathered operand, an 'e' operand's one pg_gsddmm with dout at 'v'; max / min: the masked
+    pg_gsddmm gives the winners' gradient per edge, an 'e' operand takes it, a 'u' operand its
+    sum over the out-edges (pg_gspmm copy_rhs on the transposed CSR)."""
+
+    @staticmethod
+    def forward(ctx, dg, op, reduce, lhs, rhs, lhs_target, rhs_target):
+        lhs = lhs.contiguous() if lhs is not None and op != "copy_rhs" else None
+        rhs = rhs.contiguous() if rhs is not None and op != "copy_lhs" else None
+        if lhs is not None and rhs is not None and {lhs_target, rhs_target} != {"u", "e"}:
+            raise NotImplementedError("GSpMM: a binary message takes one operand at 'u' and one at 'e'")
+        ctx.dg, ctx.op, ctx.reduce, ctx.targets = dg, op, reduce, (lhs_target, rhs_target)
+        argpos = None
+        if reduce in ("max", "min"):
+            need = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
+            out, argpos = gspmm(dg, op, reduce, lhs, rhs, lhs_target, rhs_target, want_arg=need)
+        else:
+            out = gspmm(dg, op, reduce, lhs, rhs, lhs_target, rhs_target)
+        ctx.save_for_backward(lhs, rhs, argpos)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        lhs, rhs, argpos = ctx.saved_tensors
+        dg, op = ctx.dg, ctx.op
+        d = dout.contiguous()
+        if ctx.reduce == "mean":
+            d = d / dg.fwd.ptr.diff().clamp(min=1).to(d.dtype)[:, None]
+        cmp_ = ctx.reduce in ("max", "min")
+        grads = [None, None]
+        for i, side in enumerate(("lhs", "rhs")):
+            x, y = (lhs, rhs) if i == 0 else (rhs, lhs)
+            loc = _local_grad(op, side)
+            if x is None or loc is None or not ctx.needs_input_grad[3 + i]:
+                continue
+            kind, sign = loc
+            xt, yt = ctx.targets[i], ctx.targets[1 - i]
+            if xt == "e":
+                s = _edge_term(dg, kind, d, "v", y, yt, argpos)
+            elif cmp_:
+                t = _edge_term(dg, kind, d, "v", y, yt, argpos)
+                s = gspmm(dg, "copy_rhs", "sum", None, t, "u", "e", transpose=True)
+            elif kind == "one":
+                s = gspmm(dg, "copy_lhs", "sum", d, None, "u", "e", transpose=True)
+            else:
+                s = gspmm(dg, "div" if kind == "inv" else "mul", "sum", d, y, "u", "e", transpose=True)
+            grads[i] = _finish_grad(kind, sign, s, x)
+        return None, None, None, grads[0], grads[1], None, None
+
+
+class GSDDMM(torch.autograd.Function):
+    """out[e] = op(lhs[t_l(e)], rhs[t_r(e)]), (E, F) in edge-id order, two different targets of
+    'u', 'v', 'e' (pg_gsddmm). Backward: a node operand's gradient is pg_gspmm (mul | div |
+    copy_rhs, sum) with the upstream edge gradient as the 'e' operand, on the in-CSR for an
+    operand at 'v' and on the transposed CSR for one at 'u'; an edge operand's gradient is
+    another pg_gsddmm."""
+
+    @staticmethod
+    def forward(ctx, dg, op, lhs, rhs, lhs_target, rhs_target):
+        lhs = lhs.contiguous() if lhs is not None and op != "copy_rhs" else None
+        rhs = rhs.contiguous() if rhs is not None and op != "copy_lhs" else None
+        if lhs is not None and rhs is not None and lhs_target == rhs_target:
+            raise NotImplementedError("GSDDMM: the two operands sit at different targets")
+        ctx.dg, ctx.op, ctx.targets = dg, op, (lhs_target, rhs_target)
+        ctx.save_for_backward(lhs, rhs)
+        return gsddmm(dg, op, lhs, rhs, lhs_target, rhs_target)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, de):
+        lhs, rhs = ctx.saved_tensors
+        dg, op = ctx.dg, ctx.op
+        de = de.contiguous()
+        grads = [None, None]
+        for i, side in enumerate(("lhs", "rhs")):
+            x, y = (lhs, rhs) if i == 0 else (rhs, lhs)
+            loc = _local_grad(op, side)
+            if x is None or loc is None or not ctx.needs_input_grad[2 + i]:
+                continue
+            kind, sign = loc
+            xt, yt = ctx.targets[i], ctx.targets[1 - i]
+            if xt == "e":
+                s = de if kind == "one" else _edge_term(dg, kind, de, "e", y, yt)
+            else:
+                tr = xt == "u"  # rows of the CSR = x's side; its 'u' target = the other node side
+                if kind == "one":
+                    s = gspmm(dg, "copy_rhs", "sum", None, de, "u", "e", transpose=tr)
+                elif yt == "e":
+                    s = gspmm(dg, "copy_rhs", "sum", None, de / y if kind == "inv" else de * y, "u", "e",
+                              transpose=tr)
+                elif kind == "inv":
+                    s = gspmm(dg, "div", "sum", de, y, "e", "u", transpose=tr)
+                else:
+                    s = gspmm(dg, "mul", "sum", y, de, "u", "e", transpose=tr)
+            grads[i] = _finish_grad(kind, sign, s, x)
+        return None, None, grads[0], grads[1], None, None
 
 
 def _padded(n: int, F: int, device) -> torch.Tensor:
