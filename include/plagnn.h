@@ -30,6 +30,8 @@
  *   pg_gspmm, pg_gsddmm  <- dgl.ops.gspmm / gsddmm: update_all and apply_edges with vector edge
  *                           features ((E, F) beside (N, F)), every builtin binary message, copy_e,
  *                           min; their backward. Not used by the reference: reference-unpinned.
+ *   pg_gatv2_score, _bwd <- GATv2Conv's attention score attn . leaky_relu(xl[u] + xr[v]) and its
+ *                           three gradients, fused: no (E, H, Fh) tensor. Reference-unpinned.
  *   pg_argpos_to_src     <- DGL's argX (source node id of the max) from our compact
  *                           per-row edge positions
  *   pg_sigmoid_multi_loss<- th.sigmoid (code/model.py:29) + multi_loss
@@ -273,6 +275,36 @@ int pg_spmm_sum_heads(const pg_csr_t* g, const float* A, int64_t lda, int32_t H,
 int pg_sddmm_dot_heads(const pg_csr_t* g, const float* Dm, int64_t ldd, const float* X,
                        int64_t ldx, int32_t H, int64_t Fh, float* de, int64_t lde,
                        pg_stream_t stream);
+
+/* GATv2 attention scores (Brody, Alon, Yahav 2022; dgl.nn.pytorch.GATv2Conv), fused: no
+ * [nnz][H*Fh] tensor exists, forward or backward. Conventions of the multi-head family above
+ * (slot order, 1 <= H <= 64, Fh >= 1); attn is [H*Fh], lrelu(x) = x > 0 ? x : slope * x and
+ * lrelu'(x) = x > 0 ? 1 : slope (0 counts as negative).
+ *
+ *   s[k,h] = sum_{d < Fh} attn[h*Fh + d] * lrelu(XL[col[k], h*Fh + d] + XR[v, h*Fh + d])
+ *
+ * One wave per schedule item; every s[k,h] is written exactly once (a head that straddles
+ * 256-column feature tiles is accumulated inside the wave), no workspace. The vector path
+ * needs Fh % 4 == 0, ldl and ldr multiples of 4 and XL, XR, attn 16-byte aligned; anything
+ * else takes a scalar path (one (entry, head) per lane, d ascending). */
+int pg_gatv2_score(const pg_csr_t* g, const float* XL, int64_t ldl, const float* XR, int64_t ldr,
+                   const float* attn, int32_t H, int64_t Fh, float slope, float* s, int64_t lds,
+                   pg_stream_t stream);
+/* One backward pass over the CSR g, which is the in-CSR or its transpose: the pre-activation
+ * t_k = Xown[r] + Xgat[col[k]] is recomputed for every entry k of row r, and with
+ * e(k) = eslot ? eslot[k] : k
+ *   dXown[r, f] = attn[f] * sum_{k in row r} ds[e(k), h(f)] * lrelu'(t_k[f])   (if dXown)
+ *   dattn[f]    = sum_k ds[e(k), h(f)] * lrelu(t_k[f])                          (if dattn)
+ * On the in-CSR (Xown = XR, Xgat = XL) dXown is dXR; on the transposed CSR with the operands
+ * swapped it is dXL; dattn comes out of either pass. Both outputs NULL: nothing is done.
+ * Split rows: partial sums in workspace slots, combined in slot order. dattn: one partial row
+ * per workgroup, reduced in workgroup order by two small launches. No atomics; bitwise
+ * reproducible. Workspace: pg_gatv2_bwd_workspace(g, H, Fh, dattn != NULL) bytes. */
+size_t pg_gatv2_bwd_workspace(const pg_csr_t* g, int32_t H, int64_t Fh, int with_dattn);
+int pg_gatv2_bwd(const pg_csr_t* g, const float* ds, int64_t ldds, const float* Xown, int64_t ldown,
+                 const float* Xgat, int64_t ldgat, const float* attn, int32_t H, int64_t Fh,
+                 float slope, float* dXown, int64_t lddx, float* dattn, void* ws, size_t ws_bytes,
+                 pg_stream_t stream);
 
 /* g-SpMM / g-SDDMM (DGL's gspmm / gsddmm): messages with vector edge features, f32.
  * Binary operator of a message z = op(l, r), the reducer, and where an operand row of entry
@@ -618,6 +650,14 @@ int pg_gspmm_cpu(const pg_csr_t* g, int op, int reduce, const float* L, int64_t 
 int pg_gsddmm_cpu(const pg_csr_t* g, int op, const float* L, int64_t ldl, int lt, const float* R,
                   int64_t ldr, int rt, const int32_t* eidx, int64_t F, float* out, int64_t ldo,
                   const void* argpos, int64_t lda, int arg_kind);
+/* pg_gatv2_score / pg_gatv2_bwd on host pointers: every row reduced in ascending k, dot
+ * products in ascending d, dattn in ascending k per column; OpenMP over rows (dattn: over
+ * columns); no work schedule, no workspace. */
+int pg_gatv2_score_cpu(const pg_csr_t* g, const float* XL, int64_t ldl, const float* XR, int64_t ldr,
+                       const float* attn, int32_t H, int64_t Fh, float slope, float* s, int64_t lds);
+int pg_gatv2_bwd_cpu(const pg_csr_t* g, const float* ds, int64_t ldds, const float* Xown,
+                     int64_t ldown, const float* Xgat, int64_t ldgat, const float* attn, int32_t H,
+                     int64_t Fh, float slope, float* dXown, int64_t lddx, float* dattn);
 
 /* ---------------- device: §8f — edge clustering coefficient ---------------- */
 
@@ -703,7 +743,9 @@ int pg_version(void); /* 2: pg_csr_t.einv; 3: pg_spmm_max_bwd fwd_out; 5: no in-
                          pg_gemm_f32_rows, pg_spmm_max_bwd_rows[_bf16] (the top layer's
                          backward on the train rows only);
                          13 also: pg_gspmm, pg_gspmm_workspace, pg_gsddmm and their _cpu
-                         twins (vector edge features) */
+                         twins (vector edge features);
+                         13 also: pg_gatv2_score, pg_gatv2_bwd, pg_gatv2_bwd_workspace and
+                         the _cpu twins of the first two (fused GATv2 attention scores) */
 
 #ifdef __cplusplus
 }

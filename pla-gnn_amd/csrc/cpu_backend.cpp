@@ -419,4 +419,85 @@ int pg_sddmm_dot_heads_cpu(const pg_csr_t* g, const float* Dm, int64_t ldd, cons
   return pg::ok();
 }
 
+// ---- GATv2 attention scores: t_k recomputed from the two node rows, nothing edge-sized ------
+int pg_gatv2_score_cpu(const pg_csr_t* g, const float* XL, int64_t ldl, const float* XR, int64_t ldr,
+                       const float* attn, int32_t H, int64_t Fh, float slope, float* s, int64_t lds) {
+  PG_TRY(pg::check_csr(g, "pg_gatv2_score_cpu", false));
+  PG_TRY(pg::check_heads(g, "pg_gatv2_score_cpu", H, {lds}));
+  PG_TRY(pg::check_head_features("pg_gatv2_score_cpu", H, Fh, {ldl, ldr}));
+  if (g->nnz == 0 || g->n_rows == 0) return pg::ok();
+  if (!s || !XL || !XR || !attn) return pg::set_error(PG_ERR_INVALID, "pg_gatv2_score_cpu: NULL buffer");
+  if (s == XL || s == XR || s == attn)
+    return pg::set_error(PG_ERR_INVALID, "pg_gatv2_score_cpu: the output aliases an input");
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t v = 0; v < g->n_rows; ++v) {
+    const float* r = XR + v * ldr;
+    for (int32_t k = g->ptr[v]; k < g->ptr[v + 1]; ++k) {
+      const float* l = XL + (int64_t)g->col[k] * ldl;
+      for (int32_t h = 0; h < H; ++h) {
+        float acc = 0.f;
+        for (int64_t d = h * Fh; d < (h + 1) * Fh; ++d) {
+          const float t = l[d] + r[d];
+          acc += attn[d] * (t > 0.f ? t : slope * t);
+        }
+        s[(int64_t)k * lds + h] = acc;
+      }
+    }
+  }
+  return pg::ok();
+}
+
+int pg_gatv2_bwd_cpu(const pg_csr_t* g, const float* ds, int64_t ldds, const float* Xown, int64_t ldown,
+                     const float* Xgat, int64_t ldgat, const float* attn, int32_t H, int64_t Fh, float slope,
+                     float* dXown, int64_t lddx, float* dattn) {
+  PG_TRY(pg::check_csr(g, "pg_gatv2_bwd_cpu", false));
+  PG_TRY(pg::check_heads(g, "pg_gatv2_bwd_cpu", H, {ldds}));
+  PG_TRY(pg::check_head_features("pg_gatv2_bwd_cpu", H, Fh, {ldown, ldgat, dXown ? lddx : (int64_t)H * Fh}));
+  if (!dXown && !dattn) return pg::ok();
+  const int64_t F = (int64_t)H * Fh;
+  if (g->n_rows == 0) {
+    if (dattn)
+      for (int64_t f = 0; f < F; ++f) dattn[f] = 0.f;
+    return pg::ok();
+  }
+  if (!Xown || !Xgat || !attn || (g->nnz > 0 && !ds))
+    return pg::set_error(PG_ERR_INVALID, "pg_gatv2_bwd_cpu: NULL buffer");
+  if ((dXown && (dXown == Xown || dXown == Xgat || dXown == attn || dXown == ds)) ||
+      (dattn && (dattn == Xown || dattn == Xgat || dattn == attn || dattn == ds || dattn == dXown)))
+    return pg::set_error(PG_ERR_INVALID, "pg_gatv2_bwd_cpu: an output aliases an input");
+  if (dXown) {  // attn factored out of the row sum, as the device kernel
+#pragma omp parallel for schedule(dynamic, 64)
+    for (int64_t r = 0; r < g->n_rows; ++r) {
+      const float* own = Xown + r * ldown;
+      float* o = dXown + r * lddx;
+      for (int64_t f = 0; f < F; ++f) o[f] = 0.f;
+      for (int32_t k = g->ptr[r]; k < g->ptr[r + 1]; ++k) {
+        const float* x = Xgat + (int64_t)g->col[k] * ldgat;
+        const float* w = ds + (int64_t)(g->eslot ? g->eslot[k] : k) * ldds;
+        for (int32_t h = 0; h < H; ++h) {
+          const float wsl = w[h] * slope;
+          for (int64_t f = h * Fh; f < (h + 1) * Fh; ++f) o[f] += (x[f] + own[f]) > 0.f ? w[h] : wsl;
+        }
+      }
+      for (int64_t f = 0; f < F; ++f) o[f] = attn[f] * o[f];
+    }
+  }
+  if (dattn) {  // a column's terms in ascending k, columns in parallel
+#pragma omp parallel for schedule(static)
+    for (int64_t f = 0; f < F; ++f) {
+      const int64_t h = f / Fh;
+      float acc = 0.f;
+      for (int64_t r = 0; r < g->n_rows; ++r) {
+        const float own = Xown[r * ldown + f];
+        for (int32_t k = g->ptr[r]; k < g->ptr[r + 1]; ++k) {
+          const float t = Xgat[(int64_t)g->col[k] * ldgat + f] + own;
+          acc += ds[(int64_t)(g->eslot ? g->eslot[k] : k) * ldds + h] * (t > 0.f ? t : slope * t);
+        }
+      }
+      dattn[f] = acc;
+    }
+  }
+  return pg::ok();
+}
+
 }  // extern "C"

@@ -2,7 +2,8 @@
 // SpMMCmpCsr<copy_lhs|u_mul_e, Max>, reached from SAGEConv('pool') at
 // code/model.py:20/22/24), its backward (DGL GSpMM.backward scatter_add_ through argX,
 // reached from code/train.py:204), the sum/mean variants, SDDMM, multi-head attention and
-// g-SpMM / g-SDDMM for vector edge features (DGL's gspmm / gsddmm, at the end of the file).
+// g-SpMM / g-SDDMM for vector edge features (DGL's gspmm / gsddmm) and the fused GATv2
+// attention scores (both at the end of the file).
 //
 // Work decomposition: one 64-lane wave per schedule item {row, k0, k1, slot}. A row
 // longer than the schedule's chunk is cut into several items whose partial results go
@@ -3200,6 +3201,379 @@ int pg_gsddmm(const pg_csr_t* g, int op, const float* L, int64_t ldl, int lt, co
                         : dispatch_gop(op, [&](auto o) { return by_mask(std::integral_constant<int, 1>{}, o); });
   if (rc != PG_OK) return pg::set_error(rc, "pg_gsddmm: bad op %d", op);
   return hip_status("pg_gsddmm");
+}
+
+}  // extern "C"
+
+// ---- GATv2 attention scores, fused ----------------------------------------------------------
+// s[k,h] = sum_d attn[h,d] * lrelu(XL[col[k],h,d] + XR[v,h,d]): the non-linearity sits between
+// the add and the contraction, so the score does not factor into per-node scalars. Forward
+// and backward recompute the pre-activation t_k from the two node rows; no [nnz][H*Fh] tensor
+// is ever formed.
+namespace {
+
+__device__ __forceinline__ float lrelu(float x, float slope) { return x > 0.f ? x : slope * x; }
+
+// Forward, vector path (Fh % 4 == 0): one wave per schedule item, 256 columns (one float4 per
+// lane) per feature tile, a lane's four columns in one head. U gathered XL rows are in flight
+// before any is used; the item's XR tile and the attn tile stay in registers when F fits one
+// tile. The lanes of a head are consecutive, so a segmented shuffle reduction (offsets 1, 2,
+// ... below the lanes a head can span) leaves each head's sum in its first lane. A head that
+// runs past the tile's end is not stored: its partial sum is carried (wave-uniform) into the
+// next tile, where lane 0 continues it. The tiles of a batch are walked inside the wave, so
+// each s[k,h] is written once, by one lane, in a fixed order.
+__global__ __launch_bounds__(kBlock) void gatv2_score_kernel(
+    const int32_t* __restrict__ col, const int4* __restrict__ items, int n_items,
+    const float* __restrict__ XL, int64_t ldl, const float* __restrict__ XR, int64_t ldr,
+    const float* __restrict__ attn, int F, int Fh, float slope, float* __restrict__ s, int64_t lds) {
+  constexpr int U = 8, W = 4;
+  constexpr int T = kWave * W;
+  const int it = blockIdx.x * kWavesPerBlock + wave_id_uniform();
+  if (it >= n_items) return;
+  const int4 item = items[it];
+  const int row = item.x, k0 = item.y, k1 = item.z;
+  const int lane = lane_id();
+  const float* orow = XR + (int64_t)row * ldr;
+  const bool one_tile = F <= T;
+  const int seg = min(kWave, Fh / W);  // lanes a head can span inside a tile
+  float own[W] = {0.f, 0.f, 0.f, 0.f}, at[W] = {0.f, 0.f, 0.f, 0.f};
+  int head = -1;  // lanes past F: a segment of their own, never stored
+  if (one_tile) {
+    load_tile<W>(orow, lane * W, F, own, 0.f);
+    load_tile<W>(attn, lane * W, F, at, 0.f);
+    head = lane * W < F ? lane * W / Fh : -1;
+  }
+
+  for (int kw = k0; kw < k1; kw += kWave) {
+    const int nw = min(kWave, k1 - kw);
+    const int idxv = col[kw + min(lane, nw - 1)];
+    for (int j = 0; j < nw; j += U) {
+      const int nv = min(U, nw - j);
+      float carry[U];
+#pragma unroll
+      for (int e = 0; e < U; ++e) carry[e] = 0.f;
+      int carry_h = -1;
+      for (int f0 = 0; f0 < F; f0 += T) {
+        const int f = f0 + lane * W;
+        if (!one_tile) {
+          load_tile<W>(orow, f, F, own, 0.f);
+          load_tile<W>(attn, f, F, at, 0.f);
+          head = f < F ? f / Fh : -1;
+        }
+        float v[U][W];
+#pragma unroll
+        for (int e = 0; e < U; ++e)
+          load_tile<W>(XL + (int64_t)bcast(idxv, j + min(e, nv - 1)) * ldl, f, F, v[e], 0.f);
+        float p[U];
+#pragma unroll
+        for (int e = 0; e < U; ++e) {
+          float a = 0.f;
+#pragma unroll
+          for (int i = 0; i < W; ++i) a += at[i] * lrelu(v[e][i] + own[i], slope);
+          p[e] = a;
+        }
+        for (int o = 1; o < seg; o <<= 1) {
+          const int hn = __shfl_down(head, o);  // by every lane, before the lane test: a shuffle
+          const bool same = (lane + o < kWave) & (hn == head);  // under a lane mask reads dead lanes
+#pragma unroll
+          for (int e = 0; e < U; ++e) {
+            const float q = __shfl_down(p[e], o);
+            if (same) p[e] += q;
+          }
+        }
+        const int hprev = __shfl_up(head, 1);
+        const bool first = head >= 0 && (lane == 0 || hprev != head);
+        if (lane == 0 && head == carry_h) {
+#pragma unroll
+          for (int e = 0; e < U; ++e) p[e] = carry[e] + p[e];
+        }
+        const int fend = min(F, f0 + T);
+        const int hl = (fend - 1) / Fh;               // the tile's last head
+        const bool ends = (hl + 1) * Fh <= fend;      // ... is complete here
+        if (first && (head != hl || ends)) {
+#pragma unroll
+          for (int e = 0; e < U; ++e)
+            if (e < nv) s[(int64_t)(kw + j + e) * lds + head] = p[e];
+        }
+        if (!ends) {
+          const int fl = max(0, (hl * Fh - f0) / W);  // first lane of the last head
+#pragma unroll
+          for (int e = 0; e < U; ++e) carry[e] = __shfl(p[e], fl);
+          carry_h = hl;
+        }
+      }
+    }
+  }
+}
+
+// Forward, scalar path (any Fh, ld and alignment): one (entry, head) pair per lane, the Fh
+// terms in ascending d (the host entry point's order).
+__global__ __launch_bounds__(kBlock) void gatv2_score_generic_kernel(
+    const int32_t* __restrict__ col, const int4* __restrict__ items, int n_items,
+    const float* __restrict__ XL, int64_t ldl, const float* __restrict__ XR, int64_t ldr,
+    const float* __restrict__ attn, int H, int Fh, float slope, float* __restrict__ s, int64_t lds) {
+  const int it = blockIdx.x * kWavesPerBlock + wave_id_uniform();
+  if (it >= n_items) return;
+  const int4 item = items[it];
+  const int row = item.x, k0 = item.y, k1 = item.z;
+  const float* orow = XR + (int64_t)row * ldr;
+  const int64_t n = (int64_t)(k1 - k0) * H;
+  for (int64_t i = lane_id(); i < n; i += kWave) {
+    const int k = k0 + (int)(i / H), h = (int)(i % H);
+    const float* ah = attn + (int64_t)h * Fh;
+    const float* rh = orow + (int64_t)h * Fh;
+    const float* lh = XL + (int64_t)col[k] * ldl + (int64_t)h * Fh;
+    float acc = 0.f;
+    for (int d = 0; d < Fh; ++d) acc += ah[d] * lrelu(lh[d] + rh[d], slope);
+    s[(int64_t)k * lds + h] = acc;
+  }
+}
+
+// Backward pass over a CSR (the in-CSR: dXR; its transpose with the node operands swapped:
+// dXL), shaped as sum_heads_kernel: one wave per schedule item, 256 feature columns per wave
+// (W = 4: one float4 per lane, its columns in one head; W = 1: four columns 64 apart), wider
+// F in tiles along gridDim.y (tile index ft0 + blockIdx.y). Per entry the gathered row and
+// the edge's ds value are loaded U at a time, t = gathered + own is recomputed, and
+//   DX: acc += ds * lrelu'(t)      (attn factored out: one multiply per row, not per entry)
+//   DA: da  += ds * lrelu(t)
+// A split row's piece goes to its workspace slot for sum_merge_kernel, already scaled by
+// attn. DA: the four waves of a workgroup add their da tiles through LDS in wave order and
+// write one partial row per workgroup; colsum_rows_kernel reduces those in row order.
+template <int W, bool DX, bool DA>
+__global__ __launch_bounds__(kBlock) void gatv2_bwd_kernel(
+    const int32_t* __restrict__ col, const int32_t* __restrict__ eslot, const int4* __restrict__ items,
+    int n_items, const float* __restrict__ ds, int64_t ldds, const float* __restrict__ Xown, int64_t ldown,
+    const float* __restrict__ Xgat, int64_t ldgat, const float* __restrict__ attn, int F, int Fh, int H,
+    float slope, int ft0, float* __restrict__ dX, int64_t lddx, float* __restrict__ ws, int64_t ldw,
+    float* __restrict__ da_part, int64_t ldp) {
+  constexpr int NC = W == 4 ? 1 : 4;
+  constexpr int U = 8;
+  __shared__ float sda[DA ? kWavesPerBlock * kGTile : 1];
+  const int wv = wave_id_uniform();
+  const int it = blockIdx.x * kWavesPerBlock + wv;
+  const bool active = it < n_items;
+  if (!DA && !active) return;
+  const int lane = lane_id();
+  const int f0 = (ft0 + (int)blockIdx.y) * kGTile;
+  const int Ft = min(kGTile, F - f0);
+  float da[NC][W];
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int i = 0; i < W; ++i) da[c][i] = 0.f;
+
+  if (active) {
+    const int4 item = items[it];
+    const int row = item.x, k0 = item.y, k1 = item.z, slot = item.w;
+    float own[NC][W], acc[NC][W];
+    int hc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      const int fl = (c * kWave + lane) * W;
+      hc[c] = min((f0 + fl) / Fh, H - 1);  // lanes past F: a valid head, result not stored
+      load_tile<W>(Xown + (int64_t)row * ldown + f0, fl, Ft, own[c], 0.f);
+#pragma unroll
+      for (int i = 0; i < W; ++i) acc[c][i] = 0.f;
+    }
+    Xgat += f0;
+
+    for (int kw = k0; kw < k1; kw += kWave) {
+      const int nw = min(kWave, k1 - kw);
+      const int kl = kw + min(lane, nw - 1);
+      const int idxv = col[kl];
+      const int sv = eslot ? eslot[kl] : kl;
+      for (int j = 0; j < nw; j += U) {
+        const int nv = min(U, nw - j);
+        float v[U][NC][W];
+        float w[U][NC];
+#pragma unroll
+        for (int e = 0; e < U; ++e) {
+          const int je = j + min(e, nv - 1);
+          const float* xr = Xgat + (int64_t)bcast(idxv, je) * ldgat;
+          const float* dr = ds + (int64_t)bcast(sv, je) * ldds;
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            load_tile<W>(xr, (c * kWave + lane) * W, Ft, v[e][c], 0.f);
+            w[e][c] = dr[hc[c]];
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < U; ++e) {
+          if (e < nv) {
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+              const float wsl = w[e][c] * slope;
+#pragma unroll
+              for (int i = 0; i < W; ++i) {
+                const float t = v[e][c][i] + own[c][i];
+                if constexpr (DX) acc[c][i] += t > 0.f ? w[e][c] : wsl;
+                if constexpr (DA) da[c][i] += w[e][c] * lrelu(t, slope);
+              }
+            }
+          }
+        }
+      }
+    }
+    if constexpr (DX) {
+      float* orow = (slot < 0 ? dX + (int64_t)row * lddx : ws + (int64_t)slot * ldw) + f0;
+#pragma unroll
+      for (int c = 0; c < NC; ++c) {
+        const int fl = (c * kWave + lane) * W;
+        float at[W];
+        load_tile<W>(attn + f0, fl, Ft, at, 0.f);
+#pragma unroll
+        for (int i = 0; i < W; ++i) acc[c][i] = at[i] * acc[c][i];
+        store_tile<W>(orow, fl, Ft, acc[c]);
+      }
+    }
+  }
+  if constexpr (DA) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int i = 0; i < W; ++i) sda[wv * kGTile + (c * kWave + lane) * W + i] = da[c][i];
+    __syncthreads();
+    const int t = (int)threadIdx.x;
+    if (t < Ft) {
+      float a = sda[t];
+#pragma unroll
+      for (int q = 1; q < kWavesPerBlock; ++q) a += sda[q * kGTile + t];
+      da_part[(int64_t)blockIdx.x * ldp + f0 + t] = a;
+    }
+  }
+}
+
+// out[b, f] = sum of rows [b * R, min(n, (b + 1) * R)) of `in`, in row order: the fixed-order
+// reduction of the dattn partial rows, applied until one row is left.
+constexpr int kColsumR = 32;
+__global__ __launch_bounds__(kBlock) void colsum_rows_kernel(
+    const float* __restrict__ in, int64_t ldi, int n, int F, float* __restrict__ out, int64_t ldo) {
+  const int r0 = (int)blockIdx.x * kColsumR, r1 = min(n, r0 + kColsumR);
+  for (int f = threadIdx.x; f < F; f += kBlock) {
+    float acc = 0.f;
+    for (int r = r0; r < r1; r += 8) {
+      float v[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = in[(int64_t)min(r + e, r1 - 1) * ldi + f];
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        if (r + e < r1) acc += v[e];
+    }
+    out[(int64_t)blockIdx.x * ldo + f] = acc;
+  }
+}
+
+inline int64_t colsum_rows_out(int64_t n) { return (n + kColsumR - 1) / kColsumR; }
+
+}  // namespace
+
+extern "C" {
+
+int pg_gatv2_score(const pg_csr_t* g, const float* XL, int64_t ldl, const float* XR, int64_t ldr,
+                   const float* attn, int32_t H, int64_t Fh, float slope, float* s, int64_t lds,
+                   pg_stream_t stream) {
+  PG_TRY(pg::check_csr(g, "pg_gatv2_score", true));
+  PG_TRY(pg::check_heads(g, "pg_gatv2_score", H, {lds}));
+  PG_TRY(pg::check_head_features("pg_gatv2_score", H, Fh, {ldl, ldr}));
+  if (g->nnz == 0 || g->n_rows == 0) return pg::ok();
+  if (!s || !XL || !XR || !attn) return pg::set_error(PG_ERR_INVALID, "pg_gatv2_score: NULL buffer");
+  if (s == XL || s == XR || s == attn)
+    return pg::set_error(PG_ERR_INVALID, "pg_gatv2_score: the output aliases an input");
+  const int64_t F = (int64_t)H * Fh;
+  const TilePlan tp = plan_tiles(F, {ldl, ldr}, {XL, XR, attn});
+  const int blocks = grid_for(g->n_items);
+  hipStream_t st = (hipStream_t)stream;
+  if (tp.vec && Fh % 4 == 0)
+    hipLaunchKernelGGL(gatv2_score_kernel, dim3(blocks), dim3(kBlock), 0, st, g->col, (const int4*)g->items,
+                       (int)g->n_items, XL, ldl, XR, ldr, attn, (int)F, (int)Fh, slope, s, lds);
+  else
+    hipLaunchKernelGGL(gatv2_score_generic_kernel, dim3(blocks), dim3(kBlock), 0, st, g->col,
+                       (const int4*)g->items, (int)g->n_items, XL, ldl, XR, ldr, attn, (int)H, (int)Fh, slope, s,
+                       lds);
+  return hip_status("pg_gatv2_score");
+}
+
+// workspace: [split-row slots: n_slots x ldw][dattn partial rows: one per workgroup x ldw]
+// [their first reduction: a 32nd of them x ldw], each block 256-B padded
+size_t pg_gatv2_bwd_workspace(const pg_csr_t* g, int32_t H, int64_t Fh, int with_dattn) {
+  if (!g || H < 1 || Fh < 1) return 0;
+  const int64_t ldw = ws_ld((int64_t)H * Fh);
+  size_t n = g->n_slots > 0 ? (size_t)round_up(g->n_slots * ldw * 4, 256) : 0;
+  if (with_dattn && g->n_items > 0) {
+    const int64_t nb = grid_for(g->n_items);
+    n += (size_t)round_up(nb * ldw * 4, 256) + (size_t)round_up(colsum_rows_out(nb) * ldw * 4, 256);
+  }
+  return n;
+}
+
+int pg_gatv2_bwd(const pg_csr_t* g, const float* ds, int64_t ldds, const float* Xown, int64_t ldown,
+                 const float* Xgat, int64_t ldgat, const float* attn, int32_t H, int64_t Fh,
+                 float slope, float* dXown, int64_t lddx, float* dattn, void* ws, size_t ws_bytes,
+                 pg_stream_t stream) {
+  PG_TRY(pg::check_csr(g, "pg_gatv2_bwd", true));
+  PG_TRY(pg::check_heads(g, "pg_gatv2_bwd", H, {ldds}));
+  PG_TRY(pg::check_head_features("pg_gatv2_bwd", H, Fh, {ldown, ldgat, dXown ? lddx : (int64_t)H * Fh}));
+  if (!dXown && !dattn) return pg::ok();
+  const int64_t F = (int64_t)H * Fh;
+  hipStream_t st = (hipStream_t)stream;
+  if (g->n_rows == 0) {  // no rows: dXown is empty, dattn = 0
+    if (dattn)
+      hipLaunchKernelGGL(fill2d_kernel, dim3((unsigned)std::min<int64_t>(1024, (F + kBlock - 1) / kBlock)),
+                         dim3(kBlock), 0, st, dattn, F, (int64_t)1, (int)F, 0.f);
+    return hip_status("pg_gatv2_bwd");
+  }
+  if (!Xown || !Xgat || !attn || (g->nnz > 0 && !ds))
+    return pg::set_error(PG_ERR_INVALID, "pg_gatv2_bwd: NULL buffer");
+  if ((dXown && (dXown == Xown || dXown == Xgat || dXown == attn || dXown == ds)) ||
+      (dattn && (dattn == Xown || dattn == Xgat || dattn == attn || dattn == ds || dattn == dXown)))
+    return pg::set_error(PG_ERR_INVALID, "pg_gatv2_bwd: an output aliases an input");
+  const size_t need = pg_gatv2_bwd_workspace(g, H, Fh, dattn != nullptr);
+  PG_TRY(check_ws(ws_bytes, need, "pg_gatv2_bwd"));
+  const int64_t ldw = ws_ld(F);
+  const int64_t nb = grid_for(g->n_items);
+  const size_t slot_bytes = g->n_slots > 0 ? (size_t)round_up(g->n_slots * ldw * 4, 256) : 0;
+  float* w_slots = slot_bytes ? (float*)ws : nullptr;
+  float* part_a = dattn ? (float*)((char*)ws + slot_bytes) : nullptr;
+  float* part_b = dattn ? (float*)((char*)part_a + round_up(nb * ldw * 4, 256)) : nullptr;
+  TilePlan tp = plan_tiles(F, {ldown, ldgat, dXown ? lddx : 4}, {Xown, Xgat, attn, dXown, w_slots});
+  if (Fh % 4 != 0) tp.vec = false;  // a lane's four columns must share a head
+  const int64_t n_ft = (F + kGTile - 1) / kGTile;
+  constexpr int64_t kMaxY = 32768;
+  for (int64_t y0 = 0; y0 < n_ft; y0 += kMaxY) {
+    const dim3 grid((unsigned)nb, (unsigned)std::min<int64_t>(kMaxY, n_ft - y0));
+    auto go = [&](auto w_c, auto dx_c, auto da_c) {
+      hipLaunchKernelGGL((gatv2_bwd_kernel<decltype(w_c)::value, decltype(dx_c)::value, decltype(da_c)::value>),
+                         grid, dim3(kBlock), 0, st, g->col, g->eslot, (const int4*)g->items, (int)g->n_items, ds,
+                         ldds, Xown, ldown, Xgat, ldgat, attn, (int)F, (int)Fh, (int)H, slope, (int)y0, dXown,
+                         lddx, w_slots, ldw, part_a, ldw);
+    };
+    auto by_out = [&](auto w_c) {
+      if (dXown && dattn) go(w_c, std::true_type{}, std::true_type{});
+      else if (dXown) go(w_c, std::true_type{}, std::false_type{});
+      else go(w_c, std::false_type{}, std::true_type{});
+    };
+    if (tp.vec) by_out(std::integral_constant<int, 4>{});
+    else by_out(std::integral_constant<int, 1>{});
+  }
+  if (dXown && g->n_merges > 0)
+    hipLaunchKernelGGL(sum_merge_kernel<float>, dim3((unsigned)g->n_merges), dim3(kBlock), 0, st,
+                       (const int4*)g->merges, (int)g->n_merges, (int)F, w_slots, ldw, g->ptr, 0, nullptr, 0,
+                       dXown, lddx);
+  if (dattn) {
+    const float* src = part_a;
+    float* other = part_b;
+    int64_t n = nb;
+    do {
+      const int64_t n_out = colsum_rows_out(n);
+      float* dst = n_out == 1 ? dattn : other;
+      hipLaunchKernelGGL(colsum_rows_kernel, dim3((unsigned)n_out), dim3(kBlock), 0, st, src, ldw, (int)n, (int)F,
+                         dst, ldw);
+      other = const_cast<float*>(src);
+      src = dst;
+      n = n_out;
+    } while (n > 1);
+  }
+  return hip_status("pg_gatv2_bwd");
 }
 
 }  // extern "C"

@@ -17,7 +17,8 @@ SDDMM). Edge weights may require grad: every weighted aggregation is differentia
 respect to them, as DGL's GSpMM.backward is. Multi-head attention (reference-unpinned):
 ``apply_edges(u_add_v)``, ``dgl.ops.edge_softmax`` / ``dgl.nn.functional.edge_softmax``,
 ``u_dot_v`` and ``update_all(u_mul_e, sum)`` on (N, H, Fh) features with (E, H, 1) edge
-features, and ``dgl.nn.pytorch.GATConv`` built on them. Vector edge features
+features, ``dgl.nn.pytorch.GATConv`` built on them, and ``dgl.nn.pytorch.GATv2Conv`` on a
+fused score kernel of its own (pg_gatv2_score). Vector edge features
 (reference-unpinned): every binary builtin ``{u,v,e}_{add,sub,mul,div,dot}_{u,v,e}``, ``copy_e``
 and the ``min`` reducer on node and edge features of equal trailing shapes, ``dgl.ops.gspmm`` /
 ``gsddmm`` and ``dgl.nn.pytorch.EdgeConv`` (pg_gspmm, pg_gsddmm).

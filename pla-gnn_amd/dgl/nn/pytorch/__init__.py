@@ -1,5 +1,5 @@
-"""dgl.nn.pytorch: SAGEConv (the reference's layer, code/model.py:7, 13-15), GraphConv and
-GATConv, with DGL 0.8.2's constructor signatures, parameter names and initialisation, computed by
+"""dgl.nn.pytorch: SAGEConv (the reference's layer, code/model.py:7, 13-15), GraphConv,
+GATConv, GATv2Conv and EdgeConv, with DGL 0.8.2's constructor signatures, parameter names and initialisation, computed by
 the plagnn engine."""
 from __future__ import annotations
 
@@ -239,6 +239,97 @@ class GATConv(nn.Module):
             return rst
 
 
+class GATv2Conv(nn.Module):
+    """DGL 0.8 ``GATv2Conv(in_feats, out_feats, num_heads, feat_drop=0., attn_drop=0.,
+    negative_slope=0.2, residual=False, activation=None, allow_zero_in_degree=False, bias=True,
+    share_weights=False)`` (Brody, Alon, Yahav, "How Attentive are Graph Attention Networks?",
+    ICLR 2022): e_uv = attn . leaky_relu(fc_src(h_u) + fc_dst(h_v)) per head, softmax over the
+    in-edges of v, and the source projections fc_src(h_u) summed with those weights.
+
+    The score does not factor into per-node scalars, so it runs on its own fused kernel
+    (ops.GATv2Score: no (E, H, out) tensor, forward or backward); the softmax and the
+    aggregation are the engine's multi-head kernels. Parameters are named as DGL's (fc_src,
+    fc_dst, attn, res_fc; fc_dst is fc_src with share_weights) and initialised as DGL does
+    (xavier_normal_ with the relu gain, zero biases). As in DGL, ``bias`` is the bias of the
+    linear maps (the residual map included); the layer has no separate output bias. The
+    message is the source projection, as in the paper's eq. 7 with W split into [W_l | W_r]
+    and in DGL. Not used by the reference, and written from the paper and the DGL 0.8 module
+    as documented (DGL is not installed where this is built): reference-unpinned."""
+
+    def __init__(self, in_feats, out_feats, num_heads, feat_drop=0.0, attn_drop=0.0, negative_slope=0.2,
+                 residual=False, activation=None, allow_zero_in_degree=False, bias=True, share_weights=False):
+        super().__init__()
+        if isinstance(in_feats, tuple):
+            raise NotImplementedError("bipartite GATv2Conv is not supported")
+        self._num_heads = num_heads
+        self._in_src_feats = self._in_dst_feats = in_feats
+        self._out_feats = out_feats
+        self._allow_zero_in_degree = allow_zero_in_degree
+        self._negative_slope = float(negative_slope)
+        self.fc_src = nn.Linear(in_feats, out_feats * num_heads, bias=bias)
+        if share_weights:
+            self.fc_dst = self.fc_src
+        else:
+            self.fc_dst = nn.Linear(in_feats, out_feats * num_heads, bias=bias)
+        self.attn = nn.Parameter(torch.FloatTensor(size=(1, num_heads, out_feats)))
+        self.feat_drop = nn.Dropout(feat_drop)
+        self.attn_drop = nn.Dropout(attn_drop)
+        self.leaky_relu = nn.LeakyReLU(negative_slope)
+        if residual:
+            if in_feats != out_feats * num_heads:
+                self.res_fc = nn.Linear(in_feats, num_heads * out_feats, bias=bias)
+            else:
+                self.res_fc = nn.Identity()
+        else:
+            self.register_buffer("res_fc", None)
+        self.activation = activation
+        self.share_weights = share_weights
+        self.bias = bias
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = nn.init.calculate_gain("relu")
+        nn.init.xavier_normal_(self.fc_src.weight, gain=gain)
+        if self.bias:
+            nn.init.constant_(self.fc_src.bias, 0)
+        if not self.share_weights:
+            nn.init.xavier_normal_(self.fc_dst.weight, gain=gain)
+            if self.bias:
+                nn.init.constant_(self.fc_dst.bias, 0)
+        nn.init.xavier_normal_(self.attn, gain=gain)
+        if isinstance(self.res_fc, nn.Linear):
+            nn.init.xavier_normal_(self.res_fc.weight, gain=gain)
+            if self.bias:
+                nn.init.constant_(self.res_fc.bias, 0)
+
+    def set_allow_zero_in_degree(self, set_value):
+        self._allow_zero_in_degree = set_value
+
+    def forward(self, graph, feat, get_attention=False):
+        _check_graph(graph)
+        if isinstance(feat, tuple):
+            raise NotImplementedError("bipartite input features are not supported")
+        if not self._allow_zero_in_degree and (graph._engine_graph().in_degrees() == 0).any():
+            raise plagnn.PlagnnError("There are 0-in-degree nodes in the graph; add self-loops "
+                                     "or set allow_zero_in_degree=True")
+        H, out = self._num_heads, self._out_feats
+        dg = graph._device_graph(feat.device)
+        h = self.feat_drop(feat)
+        el = self.fc_src(h).float()
+        er = el if self.share_weights else self.fc_dst(h).float()
+        s = ops.GATv2Score.apply(el, er, self.attn, dg, H, self._negative_slope)  # (E, H), slot order
+        a = self.attn_drop(ops.EdgeSoftmax.apply(s, dg))
+        rst = ops.SumAggregateHeads.apply(el, dg, a, H).to(feat.dtype).view(-1, H, out)
+        if self.res_fc is not None:
+            rst = rst + self.res_fc(h).view(h.shape[0], -1, out)
+        if self.activation:
+            rst = self.activation(rst)
+        if get_attention:
+            # slot order -> edge-id order: eid is a permutation, so every element is written once
+            return rst, torch.empty_like(a).index_copy(0, dg.eid, a).to(feat.dtype).unsqueeze(-1)
+        return rst
+
+
 class EdgeConv(nn.Module):
     """DGL 0.8.2 ``EdgeConv(in_feat, out_feat, batch_norm=False, allow_zero_in_degree=False)``
     (Wang et al., Dynamic Graph CNN): h_v = max over in-edges (u -> v) of
@@ -282,4 +373,4 @@ class EdgeConv(nn.Module):
             return g.dstdata["x"]
 
 
-__all__ = ["SAGEConv", "GraphConv", "GATConv", "EdgeConv"]
+__all__ = ["SAGEConv", "GraphConv", "GATConv", "GATv2Conv", "EdgeConv"]

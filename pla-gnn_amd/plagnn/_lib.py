@@ -226,6 +226,12 @@ SIGNATURES = {
     "pg_gsddmm": (_i, [_csr, _i, _vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i, _vp]),
     "pg_gspmm_cpu": (_i, [_csr, _i, _i, _vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _vp, _i64, _i]),
     "pg_gsddmm_cpu": (_i, [_csr, _i, _vp, _i64, _i, _vp, _i64, _i, _vp, _i64, _vp, _i64, _vp, _i64, _i]),
+    "pg_gatv2_score": (_i, [_csr, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _f, _vp, _i64, _vp]),
+    "pg_gatv2_bwd_workspace": (_sz, [_csr, _i32, _i64, _i]),
+    "pg_gatv2_bwd": (_i, [_csr, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _f, _vp, _i64, _vp, _vp, _sz,
+                          _vp]),
+    "pg_gatv2_score_cpu": (_i, [_csr, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _f, _vp, _i64]),
+    "pg_gatv2_bwd_cpu": (_i, [_csr, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _f, _vp, _i64, _vp]),
     "pg_last_error_string": (ctypes.c_char_p, []),
     "pg_version": (_i, []),
 }

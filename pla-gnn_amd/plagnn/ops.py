@@ -284,6 +284,86 @@ def sddmm_dot_heads(dg: DeviceGraph, D: torch.Tensor, X: torch.Tensor, H: int,
     return de
 
 
+def _gatv2_args(dg: DeviceGraph, name: str, xl: torch.Tensor, xr: torch.Tensor, attn: torch.Tensor, H: int) -> int:
+    """Checked operands of the GATv2 score calls: (N, H*Fh) projections and H*Fh attention
+    weights, float32 and contiguous; returns Fh."""
+    _check_device(dg, xl, xr, attn)
+    Fh = _head_width(name, xl, dg.num_nodes, H)
+    if tuple(xr.shape) != tuple(xl.shape) or xr.dtype != torch.float32:
+        raise ValueError(f"{name}: operands {tuple(xl.shape)}, {tuple(xr.shape)}")
+    if attn.dtype != torch.float32 or attn.numel() != H * Fh or not attn.is_contiguous():
+        raise ValueError(f"{name}: attn {tuple(attn.shape)} for {H} heads of {Fh}")
+    return Fh
+
+
+def gatv2_score(dg: DeviceGraph, xl: torch.Tensor, xr: torch.Tensor, attn: torch.Tensor, H: int,
+                slope: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """GATv2 attention scores s[k, h] = sum_d attn[h, d] * leaky_relu(xl[src_k, h, d] +
+    xr[dst_k, h, d]), (E, H) in slot order (pg_gatv2_score): one fused pass, no (E, H, Fh)
+    tensor."""
+    Fh = _gatv2_args(dg, "gatv2_score", xl, xr, attn, H)
+    s = torch.empty(dg.num_edges, H, dtype=torch.float32, device=xl.device) if out is None else out
+    if _edge_heads(dg, "gatv2_score", s) != H:
+        raise ValueError(f"gatv2_score: output {tuple(s.shape)} for {H} heads")
+    args = (dg.fwd.struct(None), ptr(xl), _ld(xl), ptr(xr), _ld(xr), ptr(attn), H, Fh, float(slope), ptr(s),
+            max(_ld(s), H))
+    if dg.is_cuda:
+        call("pg_gatv2_score", *args, _stream(xl))
+    else:
+        call("pg_gatv2_score_cpu", *args)
+    return s
+
+
+def gatv2_backward_pass(dg: DeviceGraph, ds: torch.Tensor, xl: torch.Tensor, xr: torch.Tensor,
+                        attn: torch.Tensor, H: int, slope: float, transpose: bool, want_dx: bool,
+                        dattn: Optional[torch.Tensor] = None, dx: Optional[torch.Tensor] = None
+                        ) -> Optional[torch.Tensor]:
+    """One pg_gatv2_bwd pass: over the in-CSR it returns dxr, over the transposed CSR
+    (`transpose`, node operands swapped) dxl (into `dx` when given), or None without
+    `want_dx`; `dattn` (H*Fh), when given, is filled by the same pass."""
+    Fh = _gatv2_args(dg, "gatv2_backward_pass", xl, xr, attn, H)
+    _check_device(dg, ds, dattn)
+    if _edge_heads(dg, "gatv2_backward_pass", ds) != H:
+        raise ValueError(f"gatv2_backward_pass: ds {tuple(ds.shape)} for {H} heads")
+    if dattn is not None and (dattn.dtype != torch.float32 or dattn.numel() != H * Fh or not dattn.is_contiguous()):
+        raise ValueError(f"gatv2_backward_pass: dattn {tuple(dattn.shape)} for {H} heads of {Fh}")
+    own, gat = (xl, xr) if transpose else (xr, xl)
+    if not want_dx:
+        dx = None
+    elif dx is None:
+        dx = torch.empty(dg.num_nodes, H * Fh, dtype=torch.float32, device=xl.device)
+    elif tuple(dx.shape) != tuple(xl.shape) or dx.dtype != torch.float32 or dx.device != xl.device:
+        raise ValueError(f"gatv2_backward_pass: dx {tuple(dx.shape)} for operands {tuple(xl.shape)}")
+    g = (dg.bwd if transpose else dg.fwd).struct(None)
+    args = (g, ptr(ds), max(_ld(ds), H), ptr(own), _ld(own), ptr(gat), _ld(gat), ptr(attn), H, Fh,
+            float(slope), ptr(dx), _ld(dx) if want_dx else 0, ptr(dattn))
+    if dg.is_cuda:
+        ws_n = _lib.lib().pg_gatv2_bwd_workspace(g, H, Fh, int(dattn is not None))
+        ws = _workspace(ws_n, xl.device)
+        call("pg_gatv2_bwd", *args, ptr(ws), ws_n, _stream(xl))
+    else:
+        call("pg_gatv2_bwd_cpu", *args)
+    return dx
+
+
+def gatv2_score_backward(dg: DeviceGraph, ds: torch.Tensor, xl: torch.Tensor, xr: torch.Tensor,
+                         attn: torch.Tensor, H: int, slope: float, need_xl: bool = True, need_xr: bool = True,
+                         need_attn: bool = True):
+    """(dxl, dxr, dattn) of gatv2_score for the (E, H) score gradient `ds` in slot order, each
+    None unless asked for. dxr is one pass over the in-CSR, dxl the same kernel over the
+    transposed CSR; dattn rides on the first pass that runs (a pass of its own when neither
+    node gradient is wanted)."""
+    dattn = torch.empty(attn.numel(), dtype=torch.float32, device=attn.device) if need_attn else None
+    dxl = dxr = None
+    da = dattn
+    if need_xr or (need_attn and not need_xl):
+        dxr = gatv2_backward_pass(dg, ds, xl, xr, attn, H, slope, False, need_xr, da)
+        da = None
+    if need_xl:
+        dxl = gatv2_backward_pass(dg, ds, xl, xr, attn, H, slope, True, True, da)
+    return dxl, dxr, dattn
+
+
 def _gop_args(dg: DeviceGraph, name: str, op: str, lhs, rhs, lhs_target: str, rhs_target: str, targets: str):
     """Checked operands of gspmm / gsddmm: (op code, lhs, rhs, F); an operand the operator
     does not read becomes None."""
@@ -762,6 +842,32 @@ class EdgeDotHeads(torch.autograd.Function):
         d_lhs = spmm_sum_heads(ctx.dg, de, rhs, ctx.H, transpose=True) if ctx.needs_input_grad[0] else None
         d_rhs = spmm_sum_heads(ctx.dg, de, lhs, ctx.H) if ctx.needs_input_grad[1] else None
         return d_lhs, d_rhs, None, None
+
+
+class GATv2Score(torch.autograd.Function):
+    """GATv2 attention scores (gatv2_score) of (N, H*Fh) source and destination projections,
+    (E, H) in slot order, so they feed EdgeSoftmax and SumAggregateHeads with no reorder.
+    Saves xl, xr and attn only: the backward recomputes the pre-activations from the node rows
+    and runs only the passes `needs_input_grad` asks for."""
+
+    @staticmethod
+    def forward(ctx, xl, xr, attn, dg, H, slope):
+        xl, xr = xl.contiguous(), xr.contiguous()
+        flat = attn.contiguous().reshape(-1)
+        ctx.dg, ctx.H, ctx.slope, ctx.attn_shape = dg, H, float(slope), attn.shape
+        ctx.save_for_backward(xl, xr, flat)
+        return gatv2_score(dg, xl, xr, flat, H, slope)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, ds):
+        xl, xr, flat = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dxl, dxr, dattn = gatv2_score_backward(ctx.dg, ds.contiguous(), xl, xr, flat, ctx.H, ctx.slope,
+                                               need_xl=need[0], need_xr=need[1], need_attn=need[2])
+        if dattn is not None:
+            dattn = dattn.reshape(ctx.attn_shape)
+        return dxl, dxr, dattn, None, None, None
 
 
 class EdgeAdd(torch.autograd.Function):
