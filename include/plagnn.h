@@ -32,6 +32,10 @@
  *                           min; their backward. Not used by the reference: reference-unpinned.
  *   pg_gatv2_score, _bwd <- GATv2Conv's attention score attn . leaky_relu(xl[u] + xr[v]) and its
  *                           three gradients, fused: no (E, H, Fh) tensor. Reference-unpinned.
+ *   pg_sample_count,     <- dgl.sampling.sample_neighbors (uniform, without replacement, in-edges) and
+ *   pg_sample_fill,         dgl.to_block (include_dst_in_src): the per-batch work of a sampled mini-batch
+ *   pg_block_compact        loop (dgl.dataloading.NeighborSampler). Not used by the reference, which trains
+ *                           the full graph: reference-unpinned.
  *   pg_argpos_to_src     <- DGL's argX (source node id of the max) from our compact
  *                           per-row edge positions
  *   pg_sigmoid_multi_loss<- th.sigmoid (code/model.py:29) + multi_loss
@@ -353,6 +357,54 @@ int pg_gsddmm(const pg_csr_t* g, int op, const float* L, int64_t ldl, int lt, co
 int pg_argpos_to_src(const pg_csr_t* g, const void* argpos, int64_t lda, int arg_kind,
                      int64_t F, int64_t* argx, int64_t ldx, pg_stream_t stream);
 
+/* ---------------- device: neighbour sampling and block compaction ---------------- */
+
+/* Mini-batch sampling (dgl.sampling.sample_neighbors, dgl.to_block). g is the parent's in-CSR
+ * (rows = destinations, entries in ascending edge id; its schedule is not read). seeds[n_seeds]
+ * are int32 parent ids; they may repeat. A seed outside [0, g->n_rows) counts as a row without
+ * entries. fanout < 0 keeps whole rows, fanout == 0 gives empty rows.
+ *
+ * pg_sample_count: out_ptr[n_seeds + 1] = the exclusive scan of min(deg(seed_i), fanout) (int32;
+ *   the total must stay below 2^31). Workspace: pg_sample_count_workspace(n_seeds) bytes.
+ * pg_sample_fill: row i of the sampled CSR, at out_ptr[i]. A row with deg <= fanout (or
+ *   fanout < 0) is copied. Any other row keeps the `fanout` entries with the smallest
+ *   (key, edge id) pairs, key = a 32-bit stateless function of (seed64, edge id) only
+ *   (two rounds of the splitmix64 finaliser, csrc/sample_key.hpp). The kept entries are
+ *   written in ascending edge id. out_col = parent source ids, out_eid = parent edge ids;
+ *   eid[nnz] maps in-CSR slots to edge ids (NULL: the identity). The result depends on the
+ *   arguments only, never on launch shape, the row's place in seeds, or timing: it equals
+ *   pg_sample_fill_cpu bit for bit. One wave per row; the selection is a bitwise threshold
+ *   search over (key, position) with a fixed number of passes (32 + position bits). Rows up
+ *   to PG_SAMPLE_LDS_KEYS entries keep their keys in LDS. A longer row recomputes its keys in
+ *   every pass over it, so it is first narrowed: the keys below a threshold set for an
+ *   expected 2 fanout + 64 of them are counted (the threshold doubled or halved, at most 40
+ *   times, until between fanout and PG_SAMPLE_LDS_KEYS / 2 keys pass: a function of the row's
+ *   keys only), those (key, position) pairs are gathered into LDS and searched there. Only
+ *   when 2 fanout + 64 > PG_SAMPLE_LDS_KEYS / 2, or that adjustment does not settle, does
+ *   every pass of the search walk the whole row. No global workspace.
+ * Nothing is allocated or synchronised; the caller reads out_ptr[n_seeds] back between the
+ * two calls (so the pair is not captured into a graph). n_seeds == 0 and nnz == 0 succeed. */
+#define PG_SAMPLE_LDS_KEYS 2048
+size_t pg_sample_count_workspace(int64_t n_seeds);
+int pg_sample_count(const pg_csr_t* g, const int32_t* seeds, int64_t n_seeds, int32_t fanout,
+                    int32_t* out_ptr, void* ws, size_t ws_bytes, pg_stream_t stream);
+int pg_sample_fill(const pg_csr_t* g, const int32_t* eid, const int32_t* seeds, int64_t n_seeds,
+                   int32_t fanout, uint64_t seed64, const int32_t* out_ptr, int32_t* out_col,
+                   int32_t* out_eid, pg_stream_t stream);
+/* Relabel the sources of a sampled CSR into a compact block (dgl.to_block with
+ * include_dst_in_src=True): src_ids[n_dst + nnz] starts with dst_ids[n_dst] in the given order,
+ * every other parent id of col[nnz] follows in the order of its first appearance in col;
+ * col_local[k] = the position of col[k] in src_ids; *n_src_dev (int32, device) = the number of
+ * src_ids written, -1 if dst_ids holds a duplicate, -2 if an id lies outside [0, n_parent)
+ * (src_ids and col_local are then unspecified). A dense first-position map over n_parent
+ * (int32 in the workspace, filled with atomicMin, which is order-independent on integers) and
+ * one prefix sum: bitwise repeatable. Workspace: pg_block_compact_workspace(n_dst, nnz,
+ * n_parent) bytes. Nothing is allocated or synchronised. */
+size_t pg_block_compact_workspace(int64_t n_dst, int64_t nnz, int64_t n_parent);
+int pg_block_compact(const int32_t* dst_ids, int64_t n_dst, const int32_t* col, int64_t nnz,
+                     int64_t n_parent, int32_t* src_ids, int32_t* col_local, int32_t* n_src_dev,
+                     void* ws, size_t ws_bytes, pg_stream_t stream);
+
 /* ---------------- device: dense helpers of the training step ---------------- */
 
 /* y = act(y + bias) in place (bias may be NULL). */
@@ -659,6 +711,16 @@ int pg_gatv2_bwd_cpu(const pg_csr_t* g, const float* ds, int64_t ldds, const flo
                      int64_t ldown, const float* Xgat, int64_t ldgat, const float* attn, int32_t H,
                      int64_t Fh, float slope, float* dXown, int64_t lddx, float* dattn);
 
+/* The sampling primitives on host pointers: the statement of their results (the device
+ * entry points equal them bit for bit). No workspace; *n_src is a host int32. */
+int pg_sample_count_cpu(const pg_csr_t* g, const int32_t* seeds, int64_t n_seeds, int32_t fanout,
+                        int32_t* out_ptr);
+int pg_sample_fill_cpu(const pg_csr_t* g, const int32_t* eid, const int32_t* seeds, int64_t n_seeds,
+                       int32_t fanout, uint64_t seed64, const int32_t* out_ptr, int32_t* out_col,
+                       int32_t* out_eid);
+int pg_block_compact_cpu(const int32_t* dst_ids, int64_t n_dst, const int32_t* col, int64_t nnz,
+                         int64_t n_parent, int32_t* src_ids, int32_t* col_local, int32_t* n_src);
+
 /* ---------------- device: §8f — edge clustering coefficient ---------------- */
 
 /* code/data_preprocess.py:175-214 edge_clustering_coefficients on a symmetric adjacency
@@ -745,7 +807,10 @@ int pg_version(void); /* 2: pg_csr_t.einv; 3: pg_spmm_max_bwd fwd_out; 5: no in-
                          13 also: pg_gspmm, pg_gspmm_workspace, pg_gsddmm and their _cpu
                          twins (vector edge features);
                          13 also: pg_gatv2_score, pg_gatv2_bwd, pg_gatv2_bwd_workspace and
-                         the _cpu twins of the first two (fused GATv2 attention scores) */
+                         the _cpu twins of the first two (fused GATv2 attention scores);
+                         13 also: pg_sample_count, pg_sample_fill,
+                         pg_block_compact, their workspace queries and _cpu twins
+                         (neighbour sampling and block compaction) */
 
 #ifdef __cplusplus
 }

@@ -5,11 +5,16 @@
 // device choice made by the caller, never a fallback for a failed GPU call.
 // Row-parallel over destinations with OpenMP, entries in CSR order, like DGL's
 // SpMMCmpCsr CPU loop.
+#include <algorithm>
 #include <cmath>
 #include <limits>
+#include <new>
+#include <utility>
+#include <vector>
 #include <type_traits>
 
 #include "common.hpp"
+#include "sample_key.hpp"
 
 namespace {
 
@@ -497,6 +502,111 @@ int pg_gatv2_bwd_cpu(const pg_csr_t* g, const float* ds, int64_t ldds, const flo
       dattn[f] = acc;
     }
   }
+  return pg::ok();
+}
+
+// ---- neighbour sampling and block compaction: the statement of the device results
+static inline int32_t sample_row_count(const pg_csr_t* g, int32_t s, int32_t fanout) {
+  if (s < 0 || s >= g->n_rows) return 0;
+  const int32_t d = std::max(0, g->ptr[s + 1] - g->ptr[s]);
+  return (fanout >= 0 && d > fanout) ? fanout : d;
+}
+
+int pg_sample_count_cpu(const pg_csr_t* g, const int32_t* seeds, int64_t n_seeds, int32_t fanout,
+                        int32_t* out_ptr) {
+  const char* who = "pg_sample_count_cpu";
+  PG_TRY(pg::check_csr(g, who, false));
+  if (n_seeds < 0 || n_seeds > INT32_MAX || !out_ptr || (n_seeds > 0 && !seeds))
+    return pg::set_error(PG_ERR_INVALID, "%s: bad seeds / out_ptr", who);
+  int64_t run = 0;
+  for (int64_t i = 0; i < n_seeds; ++i) {
+    out_ptr[i] = (int32_t)run;
+    run += sample_row_count(g, seeds[i], fanout);
+    if (run > INT32_MAX) return pg::set_error(PG_ERR_UNSUPPORTED, "%s: more than 2^31 sampled entries", who);
+  }
+  out_ptr[n_seeds] = (int32_t)run;
+  return pg::ok();
+}
+
+int pg_sample_fill_cpu(const pg_csr_t* g, const int32_t* eid, const int32_t* seeds, int64_t n_seeds,
+                       int32_t fanout, uint64_t seed64, const int32_t* out_ptr, int32_t* out_col,
+                       int32_t* out_eid) {
+  const char* who = "pg_sample_fill_cpu";
+  PG_TRY(pg::check_csr(g, who, false));
+  if (n_seeds < 0 || n_seeds > INT32_MAX || !out_ptr || (n_seeds > 0 && !seeds))
+    return pg::set_error(PG_ERR_INVALID, "%s: bad seeds / out_ptr", who);
+  if (n_seeds == 0 || g->nnz == 0 || fanout == 0) return pg::ok();
+  if (!out_col || !out_eid) return pg::set_error(PG_ERR_INVALID, "%s: NULL output", who);
+  bool failed = false;
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t i = 0; i < n_seeds; ++i) {
+    const int32_t s = seeds[i];
+    if (s < 0 || s >= g->n_rows) continue;
+    const int32_t b = g->ptr[s], deg = g->ptr[s + 1] - b;
+    if (deg <= 0) continue;
+    const int64_t o = out_ptr[i];
+    if (fanout < 0 || deg <= fanout) {
+      for (int32_t j = 0; j < deg; ++j) {
+        out_col[o + j] = g->col[b + j];
+        out_eid[o + j] = eid ? eid[b + j] : b + j;
+      }
+      continue;
+    }
+    // the fanout smallest (key, edge id) pairs; positions ascend with the edge ids of a row
+    std::vector<std::pair<uint32_t, int32_t>> kp;
+    try {
+      kp.resize((size_t)deg);
+    } catch (const std::bad_alloc&) {
+      failed = true;
+      continue;
+    }
+    for (int32_t j = 0; j < deg; ++j) kp[(size_t)j] = {pg::sample_key(seed64, eid ? eid[b + j] : b + j), j};
+    std::nth_element(kp.begin(), kp.begin() + (fanout - 1), kp.end());
+    std::vector<int32_t> keep((size_t)fanout);
+    for (int32_t q = 0; q < fanout; ++q) keep[(size_t)q] = kp[(size_t)q].second;
+    std::sort(keep.begin(), keep.end());
+    for (int32_t q = 0; q < fanout; ++q) {
+      const int32_t j = keep[(size_t)q];
+      out_col[o + q] = g->col[b + j];
+      out_eid[o + q] = eid ? eid[b + j] : b + j;
+    }
+  }
+  if (failed) return pg::set_error(PG_ERR_HOST, "%s: out of host memory", who);
+  return pg::ok();
+}
+
+int pg_block_compact_cpu(const int32_t* dst_ids, int64_t n_dst, const int32_t* col, int64_t nnz,
+                         int64_t n_parent, int32_t* src_ids, int32_t* col_local, int32_t* n_src) {
+  const char* who = "pg_block_compact_cpu";
+  if (n_dst < 0 || nnz < 0 || n_parent < 0 || n_dst + nnz > INT32_MAX - 1 || n_parent > INT32_MAX)
+    return pg::set_error(PG_ERR_INVALID, "%s: bad sizes", who);
+  if (!n_src || (n_dst > 0 && !dst_ids) || (nnz > 0 && (!col || !col_local)) || (n_dst + nnz > 0 && !src_ids))
+    return pg::set_error(PG_ERR_INVALID, "%s: NULL buffer", who);
+  std::vector<int32_t> local;
+  try {
+    local.assign((size_t)n_parent, -1);
+  } catch (const std::bad_alloc&) {
+    return pg::set_error(PG_ERR_HOST, "%s: out of host memory", who);
+  }
+  for (int64_t i = 0; i < n_dst; ++i)
+    if (dst_ids[i] < 0 || dst_ids[i] >= n_parent) return *n_src = -2, pg::ok();
+  for (int64_t k = 0; k < nnz; ++k)
+    if (col[k] < 0 || col[k] >= n_parent) return *n_src = -2, pg::ok();
+  int32_t n = 0;
+  for (int64_t i = 0; i < n_dst; ++i) {
+    if (local[(size_t)dst_ids[i]] >= 0) return *n_src = -1, pg::ok();
+    local[(size_t)dst_ids[i]] = n;
+    src_ids[n++] = dst_ids[i];
+  }
+  for (int64_t k = 0; k < nnz; ++k) {
+    int32_t& l = local[(size_t)col[k]];
+    if (l < 0) {
+      l = n;
+      src_ids[n++] = col[k];
+    }
+    col_local[k] = l;
+  }
+  *n_src = n;
   return pg::ok();
 }
 

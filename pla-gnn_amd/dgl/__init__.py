@@ -22,6 +22,10 @@ fused score kernel of its own (pg_gatv2_score). Vector edge features
 (reference-unpinned): every binary builtin ``{u,v,e}_{add,sub,mul,div,dot}_{u,v,e}``, ``copy_e``
 and the ``min`` reducer on node and edge features of equal trailing shapes, ``dgl.ops.gspmm`` /
 ``gsddmm`` and ``dgl.nn.pytorch.EdgeConv`` (pg_gspmm, pg_gsddmm).
+Mini-batch training (reference-unpinned): ``DGLBlock`` with separate ``srcdata`` / ``dstdata``,
+``dgl.create_block``, ``dgl.to_block`` (pg_block_compact), ``dgl.sampling.sample_neighbors``
+(pg_sample_count, pg_sample_fill), ``dgl.dataloading``'s neighbour samplers and DataLoader, and
+blocks or (feat_src, feat_dst) pairs in the layers of ``dgl.nn.pytorch``.
 
 Message passing on a CUDA (HIP) device always runs in libplagnn.so; a missing library is
 an error, never a silent fallback.
@@ -41,14 +45,28 @@ from . import nn  # noqa: F401  (dgl.nn)
 __version__ = "0.8.2+plagnn"
 
 _SEED: Optional[int] = None
+_SAMPLE_CALLS = 0
 _BINARY_OPS = ("add", "sub", "mul", "div")
+NID = "_ID"  # dgl.NID: parent node ids of a block's / subgraph's nodes
+EID = "_ID"  # dgl.EID: parent edge ids of its edges
 
 
 def seed(val: int) -> None:
-    """dgl.seed: DGL seeds its own C RNG (used by samplers). Nothing on the full-graph
-    training path draws from it; the value is recorded for completeness."""
-    global _SEED
+    """dgl.seed: DGL seeds its own C RNG, the one its samplers draw from. Here it starts the
+    sampler's counter: every dgl.sampling.sample_neighbors call (one per layer of a
+    NeighborSampler) takes the next 64-bit value of a sequence fixed by `val`, so the same
+    seed gives the same blocks. Nothing on the full-graph training path draws from it."""
+    global _SEED, _SAMPLE_CALLS
     _SEED = int(val)
+    _SAMPLE_CALLS = 0
+
+
+def _next_sample_seed() -> int:
+    """The 64-bit seed of the next sampling call: a counter advanced per call, offset by
+    dgl.seed's value (the kernel's key function mixes it, so consecutive values are fine)."""
+    global _SAMPLE_CALLS
+    _SAMPLE_CALLS += 1
+    return ((_SEED or 0) * 0x9E3779B97F4A7C15 + _SAMPLE_CALLS) & 0xFFFFFFFFFFFFFFFF
 
 
 def _engine():
@@ -139,15 +157,29 @@ class DGLGraph:
         self._dst = dst.to(torch.int64)
         self._n = int(num_nodes)
         self._device = torch.device(device) if device is not None else self._src.device
-        self.ndata = _Frame(self._n, "node")
+        self._init_frames()
         self.edata = _Frame(int(self._src.numel()), "edge")
         self._csr_cache = _csr_cache if _csr_cache is not None else {}
+
+    is_block = False
+
+    def _init_frames(self):
+        self.ndata = _Frame(self._n, "node")
 
     # --- structure -------------------------------------------------------------------
     def num_nodes(self, ntype=None) -> int:
         return self._n
 
     number_of_nodes = num_nodes
+
+    def num_src_nodes(self, ntype=None) -> int:
+        return self._n
+
+    def num_dst_nodes(self, ntype=None) -> int:
+        return self._n
+
+    number_of_src_nodes = num_src_nodes
+    number_of_dst_nodes = num_dst_nodes
 
     def num_edges(self, etype=None) -> int:
         return int(self._src.numel())
@@ -221,14 +253,17 @@ class DGLGraph:
     # --- message passing ----------------------------------------------------------------
     @contextlib.contextmanager
     def local_scope(self):
-        nd, ed = dict(self.ndata), dict(self.edata)
+        frames = self._frames()
+        saved = [dict(f) for f in frames]
         try:
             yield
         finally:
-            dict.clear(self.ndata)
-            dict.update(self.ndata, nd)
-            dict.clear(self.edata)
-            dict.update(self.edata, ed)
+            for f, old in zip(frames, saved):
+                dict.clear(f)
+                dict.update(f, old)
+
+    def _frames(self):
+        return [self.ndata, self.edata]
 
     def update_all(self, message_func, reduce_func, apply_node_func=None, etype=None):
         from .function import _Message, _Reduce
@@ -244,9 +279,9 @@ class DGLGraph:
         if not self._scalar_edge_form(message_func, reduce_func):
             self._update_all_gspmm(message_func, reduce_func)
             if apply_node_func is not None:
-                self.ndata.update(apply_node_func(_NodeBatch(self)))
+                self.dstdata.update(apply_node_func(_NodeBatch(self)))
             return
-        X = self.ndata[message_func.lhs]
+        X = self.srcdata[message_func.lhs]
         ew = None
         if message_func.op == "u_mul_e":
             ew = self.edata[message_func.rhs]
@@ -254,7 +289,7 @@ class DGLGraph:
                 if ew.numel() != ew.shape[0]:
                     self._update_all_heads(X, ew, reduce_func)
                     if apply_node_func is not None:
-                        self.ndata.update(apply_node_func(_NodeBatch(self)))
+                        self.dstdata.update(apply_node_func(_NodeBatch(self)))
                     return
                 ew = ew.reshape(-1)
         shape = X.shape
@@ -266,10 +301,10 @@ class DGLGraph:
             out = eng.ops.MaxAggregate.apply(X2.float(), dg, ews)
         else:
             out = eng.ops.SumAggregate.apply(X2.float(), dg, ews, reduce_func.op == "mean")
-        out = out.to(X.dtype).reshape(shape)
-        self.ndata[reduce_func.out] = out
+        out = out.to(X.dtype).reshape((self.num_dst_nodes(),) + tuple(shape[1:]))
+        self.dstdata[reduce_func.out] = out
         if apply_node_func is not None:
-            self.ndata.update(apply_node_func(_NodeBatch(self)))
+            self.dstdata.update(apply_node_func(_NodeBatch(self)))
 
     def _scalar_edge_form(self, message_func, reduce_func) -> bool:
         """True for the forms with at most one scalar per edge (or per head) that SAGEConv,
@@ -280,19 +315,19 @@ class DGLGraph:
             return False
         if message_func.op == "copy_u":
             return True
-        X, ew = self.ndata[message_func.lhs], self.edata[message_func.rhs]
+        X, ew = self.srcdata[message_func.lhs], self.edata[message_func.rhs]
         vector = ew.dim() >= 2 and ew.numel() != ew.shape[0] and X.shape[1:] == ew.shape[1:]
         return not vector
 
     def _field(self, target: str, name: str):
-        return self.edata[name] if target == "e" else self.ndata[name]
+        return self.edata[name] if target == "e" else (self.srcdata if target == "u" else self.dstdata)[name]
 
     def _update_all_gspmm(self, message_func, reduce_func):
         """update_all on pg_gspmm: copy_e, copy_u with min, and u_<op>_e / e_<op>_u with node and
         edge features of equal trailing shapes (flattened to F), with sum / mean / max / min."""
         op = message_func.op
         if op == "copy_u":
-            kop, lt, rt, lhs, rhs = "copy_lhs", "u", "e", self.ndata[message_func.lhs], None
+            kop, lt, rt, lhs, rhs = "copy_lhs", "u", "e", self.srcdata[message_func.lhs], None
         elif op == "copy_e":
             kop, lt, rt, lhs, rhs = "copy_rhs", "u", "e", None, self.edata[message_func.lhs]
         else:
@@ -308,7 +343,7 @@ class DGLGraph:
             return None if t is None else t.reshape(t.shape[0], -1).float()
 
         out = _engine().ops.GSpMM.apply(dg, kop, reduce_func.op, flat(lhs), flat(rhs), lt, rt)
-        self.ndata[reduce_func.out] = out.to(ref.dtype).reshape((self._n,) + tuple(ref.shape[1:]))
+        self.dstdata[reduce_func.out] = out.to(ref.dtype).reshape((self.num_dst_nodes(),) + tuple(ref.shape[1:]))
 
     def _update_all_heads(self, X, ew, reduce_func):
         """update_all(u_mul_e, sum) with (N, H, Fh) features and (E, H, 1) weights, H > 1:
@@ -324,7 +359,7 @@ class DGLGraph:
         dg = self._device_graph(X.device)
         A = dg.edge_weight_slots(ew)
         out = _engine().ops.SumAggregateHeads.apply(X.reshape(n, H * Fh).float(), dg, A, H)
-        self.ndata[reduce_func.out] = out.to(X.dtype).reshape(n, H, Fh)
+        self.dstdata[reduce_func.out] = out.to(X.dtype).reshape(self.num_dst_nodes(), H, Fh)
 
     def _uv(self, device):
         """(src, dst) per edge id on `device`, uploaded once per device."""
@@ -350,22 +385,22 @@ class DGLGraph:
             return
         if func.op == "v_dot_u":  # the same dot product with the operands named the other way
             func = _Message("u_dot_v", func.rhs, func.lhs, func.out)
-        lhs, rhs = self.ndata[func.lhs], self.ndata[func.rhs]
-        if lhs.shape != rhs.shape:
+        lhs, rhs = self.srcdata[func.lhs], self.dstdata[func.rhs]
+        if lhs.shape[1:] != rhs.shape[1:]:
             raise ValueError(f"{func.op}: operand shapes {tuple(lhs.shape)} and {tuple(rhs.shape)} differ")
         dg = self._device_graph(lhs.device)
-        n = lhs.shape[0]
+        n, nr = lhs.shape[0], rhs.shape[0]
         ops = _engine().ops
         if func.op == "u_add_v":
             src, dst = self._uv(lhs.device)
-            out = ops.EdgeAdd.apply(lhs.reshape(n, -1).float(), rhs.reshape(n, -1).float(), dg, src, dst)
+            out = ops.EdgeAdd.apply(lhs.reshape(n, -1).float(), rhs.reshape(nr, -1).float(), dg, src, dst)
             self.edata[func.out] = out.to(lhs.dtype).reshape((-1,) + tuple(lhs.shape[1:]))
             return
         if lhs.dim() == 3 and lhs.shape[1] > 1:
             H = lhs.shape[1]
-            de = ops.EdgeDotHeads.apply(lhs.reshape(n, -1).float(), rhs.reshape(n, -1).float(), dg, H)
+            de = ops.EdgeDotHeads.apply(lhs.reshape(n, -1).float(), rhs.reshape(nr, -1).float(), dg, H)
         else:
-            de = ops.EdgeDot.apply(lhs.reshape(n, -1).float(), rhs.reshape(n, -1).float(), dg)
+            de = ops.EdgeDot.apply(lhs.reshape(n, -1).float(), rhs.reshape(nr, -1).float(), dg)
         # slot order -> edge-id order: eid is a permutation, so every element is written once
         out = torch.empty_like(de).index_copy(0, dg.eid, de)
         shape = (-1, lhs.shape[1], 1) if lhs.dim() == 3 else (-1, 1)
@@ -395,7 +430,7 @@ class DGLGraph:
 
 class _NodeBatch:
     def __init__(self, g: DGLGraph):
-        self.data = g.ndata
+        self.data = g.dstdata
 
 
 def _as_ids(x) -> torch.Tensor:
@@ -447,4 +482,164 @@ def remove_self_loop(g: DGLGraph, etype=None) -> DGLGraph:
     return ng
 
 
-__all__ = ["DGLGraph", "graph", "add_self_loop", "remove_self_loop", "seed", "function", "nn", "ops"]
+class _NoFrame:
+    """DGLBlock.ndata: a block has two node sets, as DGL says when ndata is touched."""
+
+    def __init__(self, what: str):
+        self._what = what
+
+    def _fail(self, *a, **k):
+        raise ValueError(f"{self._what} is ambiguous on a block (source and destination nodes are separate "
+                         "sets): use srcdata or dstdata")
+
+    __getitem__ = __setitem__ = __contains__ = __iter__ = __len__ = keys = items = values = update = pop = _fail
+
+
+class DGLBlock(DGLGraph):
+    """A bipartite message-flow graph ("block"): num_src source nodes, num_dst destination
+    nodes, edges src -> dst in local ids (edge id = position), separate srcdata / dstdata
+    frames. With include_dst_in_src (the only form built here) the first num_dst source nodes
+    are the destination nodes. The engine graph is rectangular (CSRGraph.from_coo_rect, or the
+    sampler's finished in-CSR through CSRGraph.from_in_csr)."""
+
+    is_block = True
+
+    def __init__(self, src: torch.Tensor, dst: torch.Tensor, num_src: int, num_dst: int, device=None,
+                 _csr_cache=None):
+        self._n_src, self._n_dst = int(num_src), int(num_dst)
+        super().__init__(src, dst, self._n_src + self._n_dst, device=device, _csr_cache=_csr_cache)
+
+    def _init_frames(self):
+        self._srcdata = _Frame(self._n_src, "source node")
+        self._dstdata = _Frame(self._n_dst, "destination node")
+
+    @property
+    def ndata(self):
+        return _NoFrame("ndata")
+
+    @property
+    def nodes(self):
+        raise ValueError("nodes is ambiguous on a block: use srcnodes / dstnodes")
+
+    @property
+    def srcdata(self):
+        return self._srcdata
+
+    @property
+    def dstdata(self):
+        return self._dstdata
+
+    def srcnodes(self):
+        return torch.arange(self._n_src, device=self._device)
+
+    def dstnodes(self):
+        return torch.arange(self._n_dst, device=self._device)
+
+    def num_src_nodes(self, ntype=None) -> int:
+        return self._n_src
+
+    def num_dst_nodes(self, ntype=None) -> int:
+        return self._n_dst
+
+    number_of_src_nodes = num_src_nodes
+    number_of_dst_nodes = num_dst_nodes
+
+    def in_degrees(self, v=None):
+        d = torch.bincount(self._dst.cpu(), minlength=self._n_dst).to(self._device)
+        return d if v is None else d[torch.as_tensor(v, device=self._device)]
+
+    def out_degrees(self, u=None):
+        d = torch.bincount(self._src.cpu(), minlength=self._n_src).to(self._device)
+        return d if u is None else d[torch.as_tensor(u, device=self._device)]
+
+    def is_homogeneous(self) -> bool:
+        return False
+
+    def _frames(self):
+        return [self._srcdata, self._dstdata, self.edata]
+
+    def to(self, device, **kwargs) -> "DGLBlock":
+        device = torch.device(device)
+        g = DGLBlock(self._src, self._dst, self._n_src, self._n_dst, device=device, _csr_cache=self._csr_cache)
+        for new, old in zip(g._frames(), self._frames()):
+            for k, v in old.items():
+                new[k] = v.to(device)
+        if device.type == "cuda":
+            self._engine_graph().on(device)
+        return g
+
+    def _engine_graph(self):
+        if "host" not in self._csr_cache:
+            self._csr_cache["host"] = _engine().CSRGraph.from_coo_rect(
+                self._src.cpu().numpy(), self._dst.cpu().numpy(), self._n_src, self._n_dst)
+        return self._csr_cache["host"]
+
+    def __repr__(self):
+        return (f"Block(num_src_nodes={self._n_src}, num_dst_nodes={self._n_dst}, "
+                f"num_edges={self.num_edges()})")
+
+
+def create_block(data, num_src_nodes: Optional[int] = None, num_dst_nodes: Optional[int] = None, idtype=None,
+                 device=None) -> DGLBlock:
+    """dgl.create_block((u, v), num_src_nodes, num_dst_nodes): edge i goes from source node u[i]
+    to destination node v[i]."""
+    if not (isinstance(data, tuple) and len(data) == 2):
+        raise NotImplementedError("dgl.create_block: only the (src, dst) form is supported")
+    src, dst = _as_ids(data[0]), _as_ids(data[1])
+    if src.numel() != dst.numel():
+        raise ValueError("dgl.create_block: src and dst lengths differ")
+    ns = int(num_src_nodes) if num_src_nodes is not None else (int(src.max()) + 1 if src.numel() else 0)
+    nd = int(num_dst_nodes) if num_dst_nodes is not None else (int(dst.max()) + 1 if dst.numel() else 0)
+    if src.numel() and (int(src.min()) < 0 or int(dst.min()) < 0 or int(src.max()) >= ns or int(dst.max()) >= nd):
+        raise ValueError("dgl.create_block: node id out of range")
+    b = DGLBlock(src.cpu(), dst.cpu(), ns, nd)
+    return b.to(device) if device is not None else b
+
+
+def _block_from_in_csr(ptr, col_local, num_src: int, device) -> DGLBlock:
+    """A block from a finished in-CSR on the host (numpy int32; edge id = slot): its engine graph
+    is built by CSRGraph.from_in_csr with no COO sort."""
+    import numpy as _np
+
+    num_dst = len(ptr) - 1
+    dst = _np.repeat(_np.arange(num_dst, dtype=_np.int64), _np.diff(ptr))
+    cache = {"host": _engine().CSRGraph.from_in_csr(ptr, col_local, num_src)}
+    return DGLBlock(torch.from_numpy(col_local.astype(_np.int64)), torch.from_numpy(dst), num_src, num_dst,
+                    device=device, _csr_cache=cache)
+
+
+def to_block(g: DGLGraph, dst_nodes=None, include_dst_in_src: bool = True) -> DGLBlock:
+    """dgl.to_block: the block whose destination nodes are `dst_nodes` (default: the nodes of g
+    with an in-edge, ascending) and whose source nodes are dst_nodes followed by every other
+    source of g's edges in the order of its first appearance in edge-id order (pg_block_compact).
+    Edge i of the block is edge i of g. srcdata[dgl.NID] / dstdata[dgl.NID] hold g's node ids,
+    edata[dgl.EID] g's edge ids (the ids g itself carries in edata[dgl.EID] when it is a
+    sampled frontier). Every edge of g must end in dst_nodes."""
+    if g.is_block:
+        raise NotImplementedError("dgl.to_block of a block")
+    if not include_dst_in_src:
+        raise NotImplementedError("dgl.to_block(include_dst_in_src=False) is not supported")
+    dev = g.device
+    src, dst = g._src.to(dev), g._dst.to(dev)
+    n = g.num_nodes()
+    if dst_nodes is None:
+        dst_nodes = torch.unique(dst)  # sorted
+    dst_nodes = _as_ids(dst_nodes).to(dev)
+    src_ids, col_local = _engine().ops.block_compact(dst_nodes, src, n)
+    inv = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    inv[dst_nodes] = torch.arange(dst_nodes.numel(), device=dev)
+    dst_local = inv[dst]
+    if dst.numel() and int(dst_local.min()) < 0:
+        raise ValueError("dgl.to_block: an edge ends at a node that is not in dst_nodes")
+    b = DGLBlock(col_local.to(torch.int64).cpu(), dst_local.cpu(), src_ids.numel(), dst_nodes.numel(), device=dev)
+    b.srcdata[NID] = src_ids.to(torch.int64)
+    b.dstdata[NID] = dst_nodes
+    b.edata[EID] = g.edata[EID] if EID in g.edata else torch.arange(src.numel(), device=dev)
+    return b
+
+
+from . import sampling  # noqa: E402,F401  (dgl.sampling)
+from . import dataloading  # noqa: E402,F401  (dgl.dataloading)
+
+__all__ = ["DGLGraph", "DGLBlock", "graph", "create_block", "to_block", "add_self_loop", "remove_self_loop", "seed",
+           "NID", "EID", "function", "nn", "ops", "sampling", "dataloading"]

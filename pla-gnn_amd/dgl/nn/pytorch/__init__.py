@@ -18,6 +18,26 @@ def _check_graph(graph):
         raise TypeError("expected a dgl.DGLGraph built by this package")
 
 
+def _pair_feats(in_feats):
+    """dgl.utils.expand_as_pair of a layer's in_feats: (source width, destination width)."""
+    if isinstance(in_feats, tuple):
+        return int(in_feats[0]), int(in_feats[1])
+    return in_feats, in_feats
+
+
+def _expand(graph, feat):
+    """dgl.utils.expand_as_pair(feat, graph): a (feat_src, feat_dst) pair as given (a block
+    only: a square graph here has one node frame); one tensor on a block feeds its first
+    num_dst rows to the destinations (include_dst_in_src); on a square graph both are feat."""
+    if isinstance(feat, tuple):
+        if not graph.is_block:
+            raise NotImplementedError("a (feat_src, feat_dst) pair needs a block (dgl.to_block / dgl.create_block)")
+        return feat[0], feat[1]
+    if graph.is_block:
+        return feat, feat[:graph.num_dst_nodes()]
+    return feat, feat
+
+
 class SAGEConv(nn.Module):
     """DGL 0.8.2 ``SAGEConv(in_feats, out_feats, aggregator_type, feat_drop=0., bias=True,
     norm=None, activation=None)``.
@@ -38,21 +58,17 @@ class SAGEConv(nn.Module):
                            f"But got {aggregator_type!r} instead.")
         if aggregator_type == "lstm":
             raise NotImplementedError("SAGEConv 'lstm' is not provided by this engine")
-        if isinstance(in_feats, tuple):
-            if in_feats[0] != in_feats[1]:
-                raise NotImplementedError("bipartite SAGEConv is not supported")
-            in_feats = in_feats[0]
-        self._in_src_feats = self._in_dst_feats = in_feats
+        self._in_src_feats, self._in_dst_feats = _pair_feats(in_feats)
         self._out_feats = out_feats
         self._aggre_type = aggregator_type
         self.norm = norm
         self.feat_drop = nn.Dropout(feat_drop)
         self.activation = activation
         if aggregator_type == "pool":
-            self.fc_pool = nn.Linear(in_feats, in_feats)
-        self.fc_neigh = nn.Linear(in_feats, out_feats, bias=False)
+            self.fc_pool = nn.Linear(self._in_src_feats, self._in_src_feats)
+        self.fc_neigh = nn.Linear(self._in_src_feats, out_feats, bias=False)
         if aggregator_type != "gcn":
-            self.fc_self = nn.Linear(in_feats, out_feats, bias=False)
+            self.fc_self = nn.Linear(self._in_dst_feats, out_feats, bias=False)
         if bias:
             self.bias = nn.parameter.Parameter(torch.zeros(out_feats))
         else:
@@ -70,25 +86,41 @@ class SAGEConv(nn.Module):
     def forward(self, graph, feat, edge_weight=None):
         _check_graph(graph)
         if isinstance(feat, tuple):
-            raise NotImplementedError("bipartite input features are not supported")
-        feat = self.feat_drop(feat)
-        dg = graph._device_graph(feat.device)
+            feat = (self.feat_drop(feat[0]), self.feat_drop(feat[1]))
+        else:
+            feat = self.feat_drop(feat)
+        feat_src, feat_dst = _expand(graph, feat)
+        dg = graph._device_graph(feat_src.device)
         ews = dg.edge_weight_slots(edge_weight)
-        if self._aggre_type == "pool":
-            rst = ops.SagePool.apply(feat.float(), self.fc_pool.weight, self.fc_pool.bias,
+        if self._aggre_type == "pool" and not graph.is_block:
+            rst = ops.SagePool.apply(feat_src.float(), self.fc_pool.weight, self.fc_pool.bias,
                                      self.fc_self.weight, self.fc_neigh.weight, self.bias, dg, ews)
+        elif self._aggre_type == "pool":
+            # a block: the layer as DGL composes it, the max aggregation on the engine's
+            # rectangular graph (the fused ops.SagePool assumes one node set)
+            pooled = F.relu(self.fc_pool(feat_src)).float()
+            h_neigh = ops.MaxAggregate.apply(pooled, dg, ews).to(feat_src.dtype)
+            rst = self.fc_self(feat_dst) + self.fc_neigh(h_neigh)
+            if self.bias is not None:
+                rst = rst + self.bias
         else:
             lin_before_mp = self._in_src_feats > self._out_feats
-            h = self.fc_neigh(feat) if lin_before_mp else feat
+            h = self.fc_neigh(feat_src) if lin_before_mp else feat_src
             if self._aggre_type == "mean":
                 h_neigh = ops.SumAggregate.apply(h, dg, ews, True)
             else:  # gcn: (sum of neighbours + self) / (in-degree + 1)
                 s = ops.SumAggregate.apply(h, dg, ews, False)
-                degs = torch.as_tensor(graph._engine_graph().in_degrees(), device=feat.device)
-                h_neigh = (s + h) / (degs.unsqueeze(-1).to(feat.dtype) + 1)
+                degs = torch.as_tensor(graph._engine_graph().in_degrees(), device=feat_src.device)
+                if not graph.is_block:
+                    h_self = h
+                elif isinstance(feat, tuple):
+                    h_self = self.fc_neigh(feat_dst) if lin_before_mp else feat_dst
+                else:
+                    h_self = h[:graph.num_dst_nodes()]
+                h_neigh = (s + h_self) / (degs.unsqueeze(-1).to(feat_src.dtype) + 1)
             if not lin_before_mp:
                 h_neigh = self.fc_neigh(h_neigh)
-            rst = h_neigh if self._aggre_type == "gcn" else self.fc_self(feat) + h_neigh
+            rst = h_neigh if self._aggre_type == "gcn" else self.fc_self(feat_dst) + h_neigh
             if self.bias is not None:
                 rst = rst + self.bias
         if self.activation is not None:
@@ -127,6 +159,7 @@ class GraphConv(nn.Module):
 
     def forward(self, graph, feat, weight=None, edge_weight=None):
         _check_graph(graph)
+        feat, _ = _expand(graph, feat)  # only the source features are read; norms are per side
         dg = graph._device_graph(feat.device)
         eg = graph._engine_graph()
         if not self._allow_zero_in_degree and (eg.in_degrees() == 0).any():
@@ -168,7 +201,9 @@ class GATConv(nn.Module):
                  residual=False, activation=None, allow_zero_in_degree=False, bias=True):
         super().__init__()
         if isinstance(in_feats, tuple):
-            raise NotImplementedError("bipartite GATConv is not supported")
+            # the suite pins this rejection; blocks and (feat_src, feat_dst) pairs of one width
+            # run through the shared fc, as DGL does for an int in_feats
+            raise NotImplementedError("GATConv with a tuple in_feats (separate fc_src / fc_dst) is not supported")
         self._num_heads = num_heads
         self._in_src_feats = self._in_dst_feats = in_feats
         self._out_feats = out_feats
@@ -184,8 +219,8 @@ class GATConv(nn.Module):
         else:
             self.register_buffer("bias", None)
         if residual:
-            if in_feats != out_feats * num_heads:
-                self.res_fc = nn.Linear(in_feats, num_heads * out_feats, bias=False)
+            if self._in_dst_feats != out_feats * num_heads:
+                self.res_fc = nn.Linear(self._in_dst_feats, num_heads * out_feats, bias=False)
             else:
                 self.res_fc = nn.Identity()
         else:
@@ -211,16 +246,23 @@ class GATConv(nn.Module):
         from dgl.ops import edge_softmax
 
         _check_graph(graph)
-        if isinstance(feat, tuple):
-            raise NotImplementedError("bipartite input features are not supported")
         with graph.local_scope():
             if not self._allow_zero_in_degree and (graph._engine_graph().in_degrees() == 0).any():
                 raise plagnn.PlagnnError("There are 0-in-degree nodes in the graph; add self-loops "
                                          "or set allow_zero_in_degree=True")
-            h = self.feat_drop(feat)
-            ft = self.fc(h).view(-1, self._num_heads, self._out_feats)
+            H, out = self._num_heads, self._out_feats
+            if isinstance(feat, tuple):
+                h_src, h = _expand(graph, (self.feat_drop(feat[0]), self.feat_drop(feat[1])))
+                ft = self.fc(h_src).view(-1, H, out)
+                ft_dst = self.fc(h).view(-1, H, out)
+            else:
+                h_src = h = self.feat_drop(feat)
+                ft = ft_dst = self.fc(h).view(-1, H, out)
+                if graph.is_block:  # the destinations are the first num_dst sources
+                    ft_dst = ft[:graph.num_dst_nodes()]
+                    h = h[:graph.num_dst_nodes()]
             el = (ft * self.attn_l).sum(dim=-1).unsqueeze(-1)
-            er = (ft * self.attn_r).sum(dim=-1).unsqueeze(-1)
+            er = (ft_dst * self.attn_r).sum(dim=-1).unsqueeze(-1)
             graph.srcdata.update({"ft": ft, "el": el})
             graph.dstdata.update({"er": er})
             graph.apply_edges(fn.u_add_v("el", "er", "e"))
@@ -260,24 +302,26 @@ class GATv2Conv(nn.Module):
                  residual=False, activation=None, allow_zero_in_degree=False, bias=True, share_weights=False):
         super().__init__()
         if isinstance(in_feats, tuple):
-            raise NotImplementedError("bipartite GATv2Conv is not supported")
+            # the suite pins this rejection; blocks and (feat_src, feat_dst) pairs of one width
+            # are accepted with an int in_feats
+            raise NotImplementedError("GATv2Conv with a tuple in_feats is not supported")
         self._num_heads = num_heads
         self._in_src_feats = self._in_dst_feats = in_feats
         self._out_feats = out_feats
         self._allow_zero_in_degree = allow_zero_in_degree
         self._negative_slope = float(negative_slope)
-        self.fc_src = nn.Linear(in_feats, out_feats * num_heads, bias=bias)
+        self.fc_src = nn.Linear(self._in_src_feats, out_feats * num_heads, bias=bias)
         if share_weights:
             self.fc_dst = self.fc_src
         else:
-            self.fc_dst = nn.Linear(in_feats, out_feats * num_heads, bias=bias)
+            self.fc_dst = nn.Linear(self._in_dst_feats, out_feats * num_heads, bias=bias)
         self.attn = nn.Parameter(torch.FloatTensor(size=(1, num_heads, out_feats)))
         self.feat_drop = nn.Dropout(feat_drop)
         self.attn_drop = nn.Dropout(attn_drop)
         self.leaky_relu = nn.LeakyReLU(negative_slope)
         if residual:
-            if in_feats != out_feats * num_heads:
-                self.res_fc = nn.Linear(in_feats, num_heads * out_feats, bias=bias)
+            if self._in_dst_feats != out_feats * num_heads:
+                self.res_fc = nn.Linear(self._in_dst_feats, num_heads * out_feats, bias=bias)
             else:
                 self.res_fc = nn.Identity()
         else:
@@ -307,16 +351,24 @@ class GATv2Conv(nn.Module):
 
     def forward(self, graph, feat, get_attention=False):
         _check_graph(graph)
-        if isinstance(feat, tuple):
-            raise NotImplementedError("bipartite input features are not supported")
         if not self._allow_zero_in_degree and (graph._engine_graph().in_degrees() == 0).any():
             raise plagnn.PlagnnError("There are 0-in-degree nodes in the graph; add self-loops "
                                      "or set allow_zero_in_degree=True")
         H, out = self._num_heads, self._out_feats
+        if isinstance(feat, tuple):
+            h_src, h = _expand(graph, (self.feat_drop(feat[0]), self.feat_drop(feat[1])))
+            feat = h_src
+            el = self.fc_src(h_src).float()
+            er = self.fc_dst(h).float()
+        else:
+            h_src = h = self.feat_drop(feat)
+            el = self.fc_src(h).float()
+            if graph.is_block:  # the destinations are the first num_dst sources
+                h = h[:graph.num_dst_nodes()]
+                er = el[:h.shape[0]] if self.share_weights else self.fc_dst(h).float()
+            else:
+                er = el if self.share_weights else self.fc_dst(h).float()
         dg = graph._device_graph(feat.device)
-        h = self.feat_drop(feat)
-        el = self.fc_src(h).float()
-        er = el if self.share_weights else self.fc_dst(h).float()
         s = ops.GATv2Score.apply(el, er, self.attn, dg, H, self._negative_slope)  # (E, H), slot order
         a = self.attn_drop(ops.EdgeSoftmax.apply(s, dg))
         rst = ops.SumAggregateHeads.apply(el, dg, a, H).to(feat.dtype).view(-1, H, out)
@@ -340,8 +392,9 @@ class EdgeConv(nn.Module):
 
     def __init__(self, in_feat, out_feat, batch_norm=False, allow_zero_in_degree=False):
         super().__init__()
-        if isinstance(in_feat, tuple):
-            raise NotImplementedError("bipartite input features are not supported")
+        if isinstance(in_feat, tuple):  # DGL's EdgeConv has one width too: theta reads h_v - h_u
+            raise NotImplementedError("EdgeConv takes one in_feat; a (feat_src, feat_dst) pair of that width "
+                                      "is accepted by forward on a block")
         self.batch_norm = batch_norm
         self._allow_zero_in_degree = allow_zero_in_degree
         self.theta = nn.Linear(in_feat, out_feat)
@@ -356,16 +409,16 @@ class EdgeConv(nn.Module):
         import dgl.function as fn
 
         _check_graph(g)
-        if isinstance(feat, tuple):
-            raise NotImplementedError("bipartite input features are not supported")
+        h_src, h_dst = _expand(g, feat)
         with g.local_scope():
             if not self._allow_zero_in_degree and (g._engine_graph().in_degrees() == 0).any():
                 raise plagnn.PlagnnError("There are 0-in-degree nodes in the graph; add self-loops "
                                          "or set allow_zero_in_degree=True")
-            g.srcdata["x"] = feat
+            g.srcdata["x"] = h_src
+            g.dstdata["x"] = h_dst
             g.apply_edges(fn.v_sub_u("x", "x", "theta"))
             g.edata["theta"] = self.theta(g.edata["theta"])
-            g.dstdata["phi"] = self.phi(feat)
+            g.dstdata["phi"] = self.phi(h_dst)
             g.apply_edges(fn.e_add_v("theta", "phi", "e"))
             if self.batch_norm:
                 g.edata["e"] = self.bn(g.edata["e"])

@@ -83,6 +83,7 @@ class PgPad2d(ctypes.Structure):
 
 
 PG_PAD2D_MAX = 8
+PG_SAMPLE_LDS_KEYS = 2048  # rows up to this many entries keep their sampling keys in LDS
 
 _i = ctypes.c_int
 _i32 = ctypes.c_int32
@@ -232,6 +233,14 @@ SIGNATURES = {
                           _vp]),
     "pg_gatv2_score_cpu": (_i, [_csr, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _f, _vp, _i64]),
     "pg_gatv2_bwd_cpu": (_i, [_csr, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i32, _i64, _f, _vp, _i64, _vp]),
+    "pg_sample_count_workspace": (_sz, [_i64]),
+    "pg_sample_count": (_i, [_csr, _vp, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "pg_sample_fill": (_i, [_csr, _vp, _vp, _i64, _i32, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
+    "pg_block_compact_workspace": (_sz, [_i64, _i64, _i64]),
+    "pg_block_compact": (_i, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pg_sample_count_cpu": (_i, [_csr, _vp, _i64, _i32, _vp]),
+    "pg_sample_fill_cpu": (_i, [_csr, _vp, _vp, _i64, _i32, ctypes.c_uint64, _vp, _vp, _vp]),
+    "pg_block_compact_cpu": (_i, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
     "pg_last_error_string": (ctypes.c_char_p, []),
     "pg_version": (_i, []),
 }

@@ -43,6 +43,14 @@ def default_chunk_bwd(num_nodes: int) -> int:
     return 64 if num_nodes <= 65536 else 512
 
 
+def _square_nodes(num_src: int, num_dst: int) -> int:
+    """num_nodes of a square graph; a rectangular one has num_src and num_dst instead."""
+    if num_src != num_dst:
+        raise ValueError(f"num_nodes of a rectangular graph ({num_src} sources, {num_dst} destinations): "
+                         "use num_src / num_dst")
+    return num_dst
+
+
 def _np_ptr(a: np.ndarray) -> int:
     return a.ctypes.data
 
@@ -117,7 +125,10 @@ class DeviceCsr:
 
 
 class CSRGraph:
-    """In-CSR + out-CSR of a directed graph given as COO (src -> dst), host resident."""
+    """In-CSR + out-CSR of a directed graph given as COO (src -> dst), host resident. Square
+    (``CSRGraph(src, dst, num_nodes)``: sources and destinations are one node set) or
+    rectangular (``CSRGraph.from_in_csr``: a bipartite block of num_src sources and num_dst
+    destinations)."""
 
     def __init__(self, src, dst, num_nodes: int, chunk: int = DEFAULT_CHUNK,
                  chunk_bwd: Optional[int] = DEFAULT_CHUNK_BWD, bwd_trans: Optional[bool] = None):
@@ -132,14 +143,55 @@ class CSRGraph:
         eid = np.zeros(max(E, 1), np.int32)
         call("pg_csr_from_coo", _np_ptr(src), _np_ptr(dst), E, n, n, _np_ptr(ptr), _np_ptr(col),
              _np_ptr(eid))
-        col, eid = col[:E], eid[:E]
-        tptr = np.zeros(n + 1, np.int32)
+        self._finish(ptr, col[:E], eid[:E], n, n, chunk, chunk_bwd, bwd_trans)
+
+    @classmethod
+    def from_coo_rect(cls, src, dst, num_src: int, num_dst: int, chunk: int = DEFAULT_CHUNK,
+                      chunk_bwd: Optional[int] = DEFAULT_CHUNK_BWD) -> "CSRGraph":
+        """A rectangular graph from COO (src in [0, num_src), dst in [0, num_dst)): the stable
+        sort of pg_csr_from_coo, as the square constructor (dgl.create_block)."""
+        src = np.ascontiguousarray(np.asarray(src, dtype=np.int64))
+        dst = np.ascontiguousarray(np.asarray(dst, dtype=np.int64))
+        if src.shape != dst.shape or src.ndim != 1:
+            raise ValueError("src and dst must be 1-D arrays of equal length")
+        E = len(src)
+        ptr = np.zeros(int(num_dst) + 1, np.int32)
+        col = np.zeros(max(E, 1), np.int32)
+        eid = np.zeros(max(E, 1), np.int32)
+        call("pg_csr_from_coo", _np_ptr(src), _np_ptr(dst), E, int(num_src), int(num_dst), _np_ptr(ptr),
+             _np_ptr(col), _np_ptr(eid))
+        g = cls.__new__(cls)
+        g._finish(ptr, col[:E], eid[:E], int(num_src), int(num_dst), chunk, chunk_bwd, False)
+        return g
+
+    @classmethod
+    def from_in_csr(cls, ptr, col, num_src: int, chunk: int = DEFAULT_CHUNK,
+                    chunk_bwd: Optional[int] = DEFAULT_CHUNK_BWD) -> "CSRGraph":
+        """A graph from a finished in-CSR (rows = the len(ptr) - 1 destinations, col = source ids
+        below num_src, every row in the order its entries are to be reduced in): edge id = slot,
+        no COO sort. The transpose and both schedules come from the same host calls as the
+        square constructor's. A sampled block is built this way."""
+        ptr = np.ascontiguousarray(np.asarray(ptr, dtype=np.int32))
+        col = np.ascontiguousarray(np.asarray(col, dtype=np.int32))
+        if ptr.ndim != 1 or col.ndim != 1 or len(ptr) < 1 or ptr[0] != 0 or ptr[-1] != len(col):
+            raise ValueError("from_in_csr: ptr must start at 0 and end at len(col)")
+        if len(ptr) > 1 and (np.diff(ptr) < 0).any():
+            raise ValueError("from_in_csr: ptr is not monotone")
+        g = cls.__new__(cls)
+        g._finish(ptr, col, np.arange(len(col), dtype=np.int32), int(num_src), len(ptr) - 1, chunk, chunk_bwd,
+                  False)
+        return g
+
+    def _finish(self, ptr, col, eid, num_src: int, num_dst: int, chunk, chunk_bwd, bwd_trans):
+        E = len(col)
+        tptr = np.zeros(num_src + 1, np.int32)
         tcol = np.zeros(max(E, 1), np.int32)
         tslot = np.zeros(max(E, 1), np.int32)
         tpos = np.zeros(max(E, 1), np.int32)
-        call("pg_csr_transpose", _np_ptr(ptr), _np_ptr(col), n, n, E, _np_ptr(tptr), _np_ptr(tcol),
+        colp = col if E > 0 else np.zeros(1, np.int32)
+        call("pg_csr_transpose", _np_ptr(ptr), _np_ptr(colp), num_dst, num_src, E, _np_ptr(tptr), _np_ptr(tcol),
              _np_ptr(tslot), _np_ptr(tpos))
-        self.num_nodes = n
+        self.num_src, self.num_dst = num_src, num_dst
         self.num_edges = E
         self.eid = eid  # in-CSR slot -> edge id
         # the in-CSR slots' transposed indices (pg_csr_t.epos of the in-CSR): with them the
@@ -155,14 +207,18 @@ class CSRGraph:
             einv = np.empty(E, np.int32)
             einv[tslot[:E]] = np.arange(E, dtype=np.int32)
         self.bwd_trans = einv is not None
-        self.fwd = HostCsr(ptr, col, None, n, chunk, epos=einv)
+        self.fwd = HostCsr(ptr, col, None, num_src, chunk, epos=einv)
         if chunk_bwd is None:
-            chunk_bwd = default_chunk_bwd(n)
-        self.bwd = HostCsr(tptr, tcol[:E], tslot[:E], n, chunk_bwd, epos=tpos[:E])
+            chunk_bwd = default_chunk_bwd(max(num_src, num_dst))
+        self.bwd = HostCsr(tptr, tcol[:E], tslot[:E], num_dst, chunk_bwd, epos=tpos[:E])
         # argmax records hold positions inside in-CSR rows: u16 while every row is shorter
         # than 0xFFFF entries (0xFFFF = no winner)
         self.arg_kind = _lib.PG_ARG_U16 if self.fwd.max_deg < 0xFFFF else _lib.PG_ARG_I32
         self._dev: Dict[str, "DeviceGraph"] = {}
+
+    @property
+    def num_nodes(self) -> int:
+        return _square_nodes(self.num_src, self.num_dst)
 
     def on(self, device) -> "DeviceGraph":
         device = torch.device(device)
@@ -183,13 +239,17 @@ class CSRGraph:
 class DeviceGraph:
     def __init__(self, g: CSRGraph, device: torch.device):
         self.device = device
-        self.num_nodes = g.num_nodes
+        self.num_src, self.num_dst = g.num_src, g.num_dst
         self.num_edges = g.num_edges
         self.arg_kind = g.arg_kind
         self.arg_dtype = torch.int16 if g.arg_kind == _lib.PG_ARG_U16 else torch.int32
         self.fwd = DeviceCsr(g.fwd, device)
         self.bwd = DeviceCsr(g.bwd, device)
         self.eid = torch.from_numpy(g.eid.astype(np.int64)).to(device)
+
+    @property
+    def num_nodes(self) -> int:
+        return _square_nodes(self.num_src, self.num_dst)
 
     @property
     def is_cuda(self) -> bool:

@@ -76,9 +76,9 @@ def spmm_max(dg: DeviceGraph, X: torch.Tensor, ew_slots: Optional[torch.Tensor] 
         raise TypeError("spmm_max: float32 or bfloat16 features expected")
     bf = X.dtype == torch.bfloat16
     _check_device(dg, X, ew_slots)
-    n, F = dg.num_nodes, X.shape[1]
-    if X.shape[0] != n:
-        raise ValueError(f"spmm_max: X has {X.shape[0]} rows, graph has {n} nodes")
+    n, F = dg.num_dst, X.shape[1]
+    if X.shape[0] != dg.num_src:
+        raise ValueError(f"spmm_max: X has {X.shape[0]} rows, graph has {dg.num_src} source nodes")
     if out is None:
         out = torch.empty(n, F, dtype=X.dtype, device=X.device)
     if argpos is None:
@@ -113,7 +113,7 @@ def spmm_max_backward(dg: DeviceGraph, argpos: torch.Tensor, dout: torch.Tensor,
     bf = dout.dtype == torch.bfloat16
     if bf and ((mask is not None and mask.dtype != torch.bfloat16) or not dg.is_cuda):
         raise TypeError("spmm_max_backward: bfloat16 storage (GPU) needs a bfloat16 mask")
-    n, F = dg.num_nodes, dout.shape[1]
+    n, F = dg.num_src, dout.shape[1]
     if dx is None:
         dx = torch.empty(n, F, dtype=dout.dtype, device=dout.device)
     g = dg.fwd.struct(ew_slots)
@@ -138,9 +138,9 @@ def spmm_max_backward_scatter(dg: DeviceGraph, argpos: torch.Tensor, dout: torch
     if not dg.is_cuda:
         raise ValueError("scatter backward is a GPU-only entry point")
     F = dout.shape[1]
-    dx = torch.empty(dg.num_nodes, F, dtype=torch.float32, device=dout.device)
+    dx = torch.empty(dg.num_src, F, dtype=torch.float32, device=dout.device)
     call("pg_spmm_max_bwd_scatter", dg.fwd.struct(ew_slots), ptr(argpos), _ld(argpos), dg.arg_kind,
-         ptr(dout), _ld(dout), F, ptr(dx), _ld(dx), dg.num_nodes, _stream(dout))
+         ptr(dout), _ld(dout), F, ptr(dx), _ld(dx), dg.num_src, _stream(dout))
     return dx
 
 
@@ -151,8 +151,11 @@ def spmm_sum(dg: DeviceGraph, X: torch.Tensor, mean: bool = False,
     out-CSR: the backward of the forward aggregation (mean -> per-term 1/deg(dst))."""
     _check_device(dg, X, ew_slots)
     F = X.shape[1]
+    n_out, n_in = (dg.num_src, dg.num_dst) if transpose else (dg.num_dst, dg.num_src)
+    if X.shape[0] != n_in:
+        raise ValueError(f"spmm_sum: X has {X.shape[0]} rows, {n_in} expected")
     if out is None:
-        out = torch.empty(dg.num_nodes, F, dtype=torch.float32, device=X.device)
+        out = torch.empty(n_out, F, dtype=torch.float32, device=X.device)
     csr = dg.bwd if transpose else dg.fwd
     g = csr.struct(ew_slots)
     norm_mode = (2 if transpose else 1) if mean else 0
@@ -176,9 +179,10 @@ def sddmm_dot(dg: DeviceGraph, D: torch.Tensor, X: torch.Tensor, mean: bool = Fa
     _check_device(dg, D, X, argpos)
     if D.dtype != torch.float32 or X.dtype != torch.float32:
         raise TypeError("sddmm_dot: float32 operands expected")
-    n, F = dg.num_nodes, D.shape[1]
-    if D.shape[0] != n or tuple(X.shape) != (n, F):
-        raise ValueError(f"sddmm_dot: operands {tuple(D.shape)}, {tuple(X.shape)} on a graph of {n} nodes")
+    n, F = dg.num_dst, D.shape[1]
+    if D.shape[0] != n or tuple(X.shape) != (dg.num_src, F):
+        raise ValueError(f"sddmm_dot: operands {tuple(D.shape)}, {tuple(X.shape)} on a graph of {dg.num_src} "
+                         f"source and {n} destination nodes")
     if argpos is not None and (argpos.dtype != dg.arg_dtype or tuple(argpos.shape) != (n, F)):
         raise ValueError("sddmm_dot: argpos does not match the graph's record type or the operands' shape")
     de = torch.empty(dg.num_edges, dtype=torch.float32, device=D.device)
@@ -250,9 +254,10 @@ def spmm_sum_heads(dg: DeviceGraph, A: torch.Tensor, X: torch.Tensor, H: int, tr
     _check_device(dg, A, X, out)
     if _edge_heads(dg, "spmm_sum_heads", A) != H:
         raise ValueError(f"spmm_sum_heads: weights {tuple(A.shape)} for {H} heads")
-    Fh = _head_width("spmm_sum_heads", X, dg.num_nodes, H)
+    n_out, n_in = (dg.num_src, dg.num_dst) if transpose else (dg.num_dst, dg.num_src)
+    Fh = _head_width("spmm_sum_heads", X, n_in, H)
     if out is None:
-        out = torch.empty(dg.num_nodes, H * Fh, dtype=torch.float32, device=X.device)
+        out = torch.empty(n_out, H * Fh, dtype=torch.float32, device=X.device)
     g = (dg.bwd if transpose else dg.fwd).struct(None)
     args = (g, ptr(A), _ld(A), H, ptr(X), _ld(X), Fh, ptr(out), _ld(out))
     if dg.is_cuda:
@@ -270,8 +275,8 @@ def sddmm_dot_heads(dg: DeviceGraph, D: torch.Tensor, X: torch.Tensor, H: int,
     (E, H) in slot order (pg_sddmm_dot_heads): the gradient of spmm_sum_heads w.r.t. its
     weights (D = dout), and apply_edges(u_dot_v) on (N, H, Fh) operands."""
     _check_device(dg, D, X, out)
-    Fh = _head_width("sddmm_dot_heads", D, dg.num_nodes, H)
-    if tuple(X.shape) != tuple(D.shape) or X.dtype != torch.float32:
+    Fh = _head_width("sddmm_dot_heads", D, dg.num_dst, H)
+    if tuple(X.shape) != (dg.num_src, D.shape[1]) or X.dtype != torch.float32:
         raise ValueError(f"sddmm_dot_heads: operands {tuple(D.shape)}, {tuple(X.shape)}")
     de = torch.empty(dg.num_edges, H, dtype=torch.float32, device=D.device) if out is None else out
     if _edge_heads(dg, "sddmm_dot_heads", de) != H:
@@ -288,8 +293,8 @@ def _gatv2_args(dg: DeviceGraph, name: str, xl: torch.Tensor, xr: torch.Tensor, 
     """Checked operands of the GATv2 score calls: (N, H*Fh) projections and H*Fh attention
     weights, float32 and contiguous; returns Fh."""
     _check_device(dg, xl, xr, attn)
-    Fh = _head_width(name, xl, dg.num_nodes, H)
-    if tuple(xr.shape) != tuple(xl.shape) or xr.dtype != torch.float32:
+    Fh = _head_width(name, xl, dg.num_src, H)
+    if tuple(xr.shape) != (dg.num_dst, xl.shape[1]) or xr.dtype != torch.float32:
         raise ValueError(f"{name}: operands {tuple(xl.shape)}, {tuple(xr.shape)}")
     if attn.dtype != torch.float32 or attn.numel() != H * Fh or not attn.is_contiguous():
         raise ValueError(f"{name}: attn {tuple(attn.shape)} for {H} heads of {Fh}")
@@ -331,8 +336,8 @@ def gatv2_backward_pass(dg: DeviceGraph, ds: torch.Tensor, xl: torch.Tensor, xr:
     if not want_dx:
         dx = None
     elif dx is None:
-        dx = torch.empty(dg.num_nodes, H * Fh, dtype=torch.float32, device=xl.device)
-    elif tuple(dx.shape) != tuple(xl.shape) or dx.dtype != torch.float32 or dx.device != xl.device:
+        dx = torch.empty(own.shape[0], H * Fh, dtype=torch.float32, device=xl.device)
+    elif tuple(dx.shape) != tuple(own.shape) or dx.dtype != torch.float32 or dx.device != xl.device:
         raise ValueError(f"gatv2_backward_pass: dx {tuple(dx.shape)} for operands {tuple(xl.shape)}")
     g = (dg.bwd if transpose else dg.fwd).struct(None)
     args = (g, ptr(ds), max(_ld(ds), H), ptr(own), _ld(own), ptr(gat), _ld(gat), ptr(attn), H, Fh,
@@ -364,9 +369,11 @@ def gatv2_score_backward(dg: DeviceGraph, ds: torch.Tensor, xl: torch.Tensor, xr
     return dxl, dxr, dattn
 
 
-def _gop_args(dg: DeviceGraph, name: str, op: str, lhs, rhs, lhs_target: str, rhs_target: str, targets: str):
+def _gop_args(dg: DeviceGraph, name: str, op: str, lhs, rhs, lhs_target: str, rhs_target: str, targets: str,
+              transpose: bool = False):
     """Checked operands of gspmm / gsddmm: (op code, lhs, rhs, F); an operand the operator
-    does not read becomes None."""
+    does not read becomes None. 'u' rows are the sources and 'v' rows the destinations of the
+    in-CSR; on the transposed CSR the two swap."""
     if op not in _lib.PG_OP:
         raise ValueError(f"{name}: unknown operator {op!r}")
     if op == "copy_rhs":
@@ -381,12 +388,13 @@ def _gop_args(dg: DeviceGraph, name: str, op: str, lhs, rhs, lhs_target: str, rh
             continue
         if tgt not in targets:
             raise ValueError(f"{name}: {side} target {tgt!r}, one of {tuple(targets)} expected")
-        rows = dg.num_edges if tgt == "e" else dg.num_nodes
+        n_u, n_v = (dg.num_dst, dg.num_src) if transpose else (dg.num_src, dg.num_dst)
+        rows = dg.num_edges if tgt == "e" else (n_u if tgt == "u" else n_v)
         if t.dtype != torch.float32:
             raise TypeError(f"{name}: float32 operands expected")
         if t.dim() != 2 or t.shape[0] != rows or (F is not None and t.shape[1] != F):
             raise ValueError(f"{name}: {side} operand {tuple(t.shape)} at target {tgt!r} on a graph of "
-                             f"{dg.num_nodes} nodes and {dg.num_edges} edges")
+                             f"{dg.num_src} x {dg.num_dst} nodes and {dg.num_edges} edges")
         F = t.shape[1]
     _check_device(dg, lhs, rhs)
     return _lib.PG_OP[op], lhs, rhs, F
@@ -427,14 +435,14 @@ def gspmm(dg: DeviceGraph, op: str, reduce: str, lhs: Optional[torch.Tensor], rh
     the out-CSR, where 'u' is the destination of each out-edge: the source-side gradients.
     Returns out for sum / mean, (out, argpos) for max / min (argpos None with want_arg=False)."""
     name = "gspmm"
-    code, lhs, rhs, F = _gop_args(dg, name, op, lhs, rhs, lhs_target, rhs_target, "ue")
+    code, lhs, rhs, F = _gop_args(dg, name, op, lhs, rhs, lhs_target, rhs_target, "ue", transpose)
     if reduce not in ("sum", "mean", "max", "min"):
         raise ValueError(f"{name}: unknown reducer {reduce!r}")
     red = _lib.PG_RED["sum" if reduce == "mean" else reduce]
     csr = dg.bwd if transpose else dg.fwd
     g = csr.struct(None)
     emap = _edge_index(dg, eidx, transpose)
-    n = dg.num_nodes
+    n = dg.num_src if transpose else dg.num_dst
     dev = (lhs if lhs is not None else rhs).device
     if out is None:
         out = torch.empty(n, F, dtype=torch.float32, device=dev)
@@ -468,7 +476,7 @@ def gsddmm(dg: DeviceGraph, op: str, lhs: Optional[torch.Tensor], rhs: Optional[
     gives ("eid": edge-id order); targets 'u' (source), 'v' (destination), 'e'. With `argpos`
     (a max / min reduce's records) the value only where the edge won, +0 elsewhere."""
     name = "gsddmm"
-    code, lhs, rhs, F = _gop_args(dg, name, op, lhs, rhs, lhs_target, rhs_target, "uve")
+    code, lhs, rhs, F = _gop_args(dg, name, op, lhs, rhs, lhs_target, rhs_target, "uve", transpose)
     csr = dg.bwd if transpose else dg.fwd
     emap = _edge_index(dg, eidx, transpose)
     dev = (lhs if lhs is not None else rhs).device
@@ -478,8 +486,8 @@ def gsddmm(dg: DeviceGraph, op: str, lhs: Optional[torch.Tensor], rhs: Optional[
     _check_device(dg, out, argpos)
     if tuple(out.shape) != (dg.num_edges, F) or out.dtype != torch.float32:
         raise ValueError(f"{name}: output {tuple(out.shape)}, ({dg.num_edges}, {F}) float32 expected")
-    if argpos is not None and (tuple(argpos.shape) != (dg.num_nodes, F) or argpos.dtype != _arg_dtype(kind)):
-        raise ValueError(f"{name}: argpos does not match ({dg.num_nodes}, {F}) / the record kind")
+    if argpos is not None and (tuple(argpos.shape) != (csr.n_rows, F) or argpos.dtype != _arg_dtype(kind)):
+        raise ValueError(f"{name}: argpos does not match ({csr.n_rows}, {F}) / the record kind")
     args = (csr.struct(None), code, ptr(lhs), _ld(lhs) if lhs is not None else 0, _lib.PG_TGT[lhs_target],
             ptr(rhs), _ld(rhs) if rhs is not None else 0, _lib.PG_TGT[rhs_target], ptr(emap), F,
             ptr(out), _ld(out) if out.numel() else max(F, 1), ptr(argpos),
@@ -495,10 +503,11 @@ def segment_sum(dg: DeviceGraph, de_slots: torch.Tensor, transpose: bool = False
     """Sums of (E, T) edge values in slot order over the in-edges of each node (transpose: the
     out-edges), (N, T): spmm_sum_heads with Fh = 1 and X = 1, at most 64 columns per call."""
     E, T = de_slots.shape
-    out = torch.empty(dg.num_nodes, T, dtype=torch.float32, device=de_slots.device)
+    n_out, n_in = (dg.num_src, dg.num_dst) if transpose else (dg.num_dst, dg.num_src)
+    out = torch.empty(n_out, T, dtype=torch.float32, device=de_slots.device)
     for c0 in range(0, T, 64):
         Hc = min(64, T - c0)
-        ones = torch.ones(dg.num_nodes, Hc, dtype=torch.float32, device=de_slots.device)
+        ones = torch.ones(n_in, Hc, dtype=torch.float32, device=de_slots.device)
         spmm_sum_heads(dg, de_slots[:, c0:c0 + Hc], ones, Hc, transpose=transpose, out=out[:, c0:c0 + Hc])
     return out
 
@@ -514,6 +523,77 @@ def argpos_to_src(dg: DeviceGraph, argpos: torch.Tensor) -> torch.Tensor:
     else:
         call("pg_argpos_to_src_cpu", g, ptr(argpos), _ld(argpos), dg.arg_kind, F, ptr(argx), F)
     return argx
+
+
+# ------------------------------------------------------------------ sampling
+def _ids32(t, device, name: str) -> torch.Tensor:
+    t = torch.as_tensor(t)
+    if t.dtype not in (torch.int32, torch.int64) or t.dim() != 1:
+        raise TypeError(f"{name}: a 1-D int32 / int64 id tensor expected")
+    return t.to(device=device, dtype=torch.int32).contiguous()
+
+
+def sample_neighbors(dg: DeviceGraph, seeds, fanout: int, seed: int):
+    """Up to `fanout` in-edges of every seed node, without replacement (pg_sample_count +
+    pg_sample_fill): (ptr, col, eid) of the sampled in-CSR, int32 on the graph's device, row i
+    for seeds[i], col = parent source ids, eid = parent edge ids ascending in each row.
+    fanout < 0 keeps whole rows. The result is a function of (graph, seeds, fanout, seed)
+    only. One device-to-host read lies between the two calls: the entry count, and with it
+    whether a seed lies outside the graph (ValueError; the count kernel itself takes such a seed
+    as a row without entries)."""
+    seeds = _ids32(seeds, dg.device, "sample_neighbors")
+    n = seeds.numel()
+    fanout, seed = int(fanout), int(seed) & 0xFFFFFFFFFFFFFFFF
+    g = dg.fwd.struct(None)
+    emap = dg.edge_map()
+    out_ptr = torch.empty(n + 1, dtype=torch.int32, device=dg.device)
+    if dg.is_cuda:
+        ws_n = _lib.lib().pg_sample_count_workspace(n)
+        ws = _workspace(ws_n, dg.device)
+        call("pg_sample_count", g, ptr(seeds), n, fanout, ptr(out_ptr), ptr(ws), ws_n, _stream(out_ptr))
+    else:
+        call("pg_sample_count_cpu", g, ptr(seeds), n, fanout, ptr(out_ptr))
+    bad = ((seeds < 0) | (seeds >= dg.num_dst)).any().to(torch.int32).reshape(1)
+    total, bad = torch.cat([out_ptr[n:], bad]).tolist()  # one read-back for both
+    if bad:
+        raise ValueError(f"sample_neighbors: seed ids outside [0, {dg.num_dst})")
+    col = torch.empty(total, dtype=torch.int32, device=dg.device)
+    eid = torch.empty(total, dtype=torch.int32, device=dg.device)
+    args = (g, ptr(emap), ptr(seeds), n, fanout, seed, ptr(out_ptr), ptr(col), ptr(eid))
+    if total:
+        if dg.is_cuda:
+            call("pg_sample_fill", *args, _stream(out_ptr))
+        else:
+            call("pg_sample_fill_cpu", *args)
+    return out_ptr, col, eid
+
+
+def block_compact(dst_ids, col, n_parent: int):
+    """(src_ids, col_local) of a block (pg_block_compact): src_ids = dst_ids followed by every
+    other parent id of `col` in the order of its first appearance there, col_local[k] = the
+    position of col[k] in src_ids; int32 on col's device. Duplicate dst_ids: ValueError. One
+    device-to-host read (the source count)."""
+    col = torch.as_tensor(col)
+    dev = col.device
+    col = _ids32(col, dev, "block_compact")
+    dst_ids = _ids32(dst_ids, dev, "block_compact")
+    n_dst, nnz, n_parent = dst_ids.numel(), col.numel(), int(n_parent)
+    src_ids = torch.empty(n_dst + nnz, dtype=torch.int32, device=dev)
+    col_local = torch.empty(nnz, dtype=torch.int32, device=dev)
+    n_src = torch.empty(1, dtype=torch.int32, device=dev)
+    args = (ptr(dst_ids), n_dst, ptr(col), nnz, n_parent, ptr(src_ids), ptr(col_local), ptr(n_src))
+    if dev.type == "cuda":
+        ws_n = _lib.lib().pg_block_compact_workspace(n_dst, nnz, n_parent)
+        ws = _workspace(ws_n, dev)
+        call("pg_block_compact", *args, ptr(ws), ws_n, _stream(col_local))
+    else:
+        call("pg_block_compact_cpu", *args)
+    n = int(n_src[0])
+    if n == -1:
+        raise ValueError("block_compact: dst_ids holds a duplicate")
+    if n < 0:
+        raise ValueError(f"block_compact: an id lies outside [0, {n_parent})")
+    return src_ids[:n], col_local
 
 
 # ------------------------------------------------------------------ dense
