@@ -229,7 +229,25 @@ int pg_spmm_max_bwd_scatter(const pg_csr_t* g, const void* argpos, int64_t lda, 
  *   coef_k = (ew ? ew[eslot ? eslot[k] : k] : 1)
  *   norm_mode 0: plain sum; 1: divide the row sum by the row's entry count (mean);
  *   2: each term divided by the entry count of col[k] in norm_ptr (mean backward).
- * Rows with no entries get 0. */
+ * Rows with no entries get +0. Every element out[r, f], r < n_rows, f < F, is written exactly
+ * once (nothing outside the F columns of a row is read or written, ldx, ldo >= F), without
+ * atomics, as one fixed float32 expression (the library is built without FMA contraction):
+ *   a schedule item {row, k0, k1, slot} starts at +0 and adds, for k = k0 .. k1 - 1 in
+ *     order, x = X[col[k], f] (with ew: x * coef_k; then in mode 2 that divided by
+ *     (float)(entry count of col[k])), each step one rounding;
+ *   an unsplit row (slot < 0) is its item, in mode 1 divided by (float)(the row's entry
+ *     count) when that is not 0;
+ *   a split row adds its items' partial sums (workspace slots s0 .. s0 + ns - 1 of its
+ *     merge) in slot order from +0, then in mode 1 divides by (float)(the row's entry count).
+ * So the result is bitwise reproducible, does not depend on the path taken, and on rows the
+ * schedule does not split it equals pg_spmm_sum_cpu bit for bit (which sums every row as one
+ * item). The vector path (float4 accesses, 256 columns per launch) is taken when F, ldx and
+ * ldo are multiples of 4 and X, out and ws are 16-byte aligned; the scalar path (1024 columns
+ * per launch) otherwise. F == 0 and n_rows == 0 succeed without touching a buffer. The call
+ * allocates nothing and does not synchronise (graph-capturable). PG_ERR_INVALID: ldx or ldo
+ * below F, norm_mode outside 0 .. 2, mode 2 without norm_ptr, X or out NULL with work to do
+ * (pg_spmm_sum_cpu the same); PG_ERR_WORKSPACE: ws_bytes below pg_spmm_sum_workspace(g, F)
+ * (0 for a schedule without split rows). Nothing is launched after an error. */
 size_t pg_spmm_sum_workspace(const pg_csr_t* g, int64_t F);
 int pg_spmm_sum(const pg_csr_t* g, const float* X, int64_t ldx, int64_t F, int norm_mode,
                 const int32_t* norm_ptr, float* out, int64_t ldo, void* ws, size_t ws_bytes,

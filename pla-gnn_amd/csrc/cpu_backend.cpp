@@ -268,7 +268,9 @@ int pg_spmm_sum_cpu(const pg_csr_t* g, const float* X, int64_t ldx, int64_t F, i
   if (F < 0 || ldx < F || ldo < F)
     return pg::set_error(PG_ERR_INVALID, "pg_spmm_sum_cpu: bad F/leading dims");
   if (norm_mode < 0 || norm_mode > 2 || (norm_mode == 2 && !norm_ptr))
-    return pg::set_error(PG_ERR_INVALID, "pg_spmm_sum_cpu: bad norm_mode");
+    return pg::set_error(PG_ERR_INVALID, "pg_spmm_sum_cpu: bad norm_mode %d", norm_mode);
+  if (F == 0 || g->n_rows == 0) return pg::ok();
+  if (!X || !out) return pg::set_error(PG_ERR_INVALID, "pg_spmm_sum_cpu: NULL buffer");
 #pragma omp parallel for schedule(dynamic, 64)
   for (int64_t r = 0; r < g->n_rows; ++r) {
     float* o = out + r * ldo;

@@ -5,7 +5,8 @@
 // schedules) and the _cpu message-passing entry points on random multigraphs with empty
 // rows, duplicate edges, explicit self-loops and a hub row that the schedule splits, and
 // checks them against the oracle (bit-exact max / argmax, backward within summation order);
-// then the oracle's ECC and perturbation loops on small inputs. Any sanitizer report aborts
+// pg_spmm_sum_cpu also on the transposed CSR (weighted, mean-backward form, strided operands
+// with guard columns) against a double-precision loop, and its error returns; then the oracle's ECC and perturbation loops on small inputs. Any sanitizer report aborts
 // the process with a non-zero status.
 #include <algorithm>
 #include <cmath>
@@ -153,6 +154,50 @@ static void run_case(int64_t n, int64_t e, int64_t hub, int64_t F, int chunk, bo
     const float ref = X[i] > 0.f ? odx[i] : 0.f;
     CHECK(std::fabs(dx[i] - ref) <= 1e-5f * (1.f + std::fabs(ref)), "max bwd (%ld) %g vs %g", (long)i, dx[i], ref);
     CHECK(std::fabs(sum[i] - osum[i]) <= 1e-5f * (1.f + std::fabs(osum[i])), "mean (%ld)", (long)i);
+  }
+
+  // pg_spmm_sum_cpu on the transposed CSR (eslot set): plain and mode 2 with norm_ptr, weighted,
+  // ldx and ldo larger than F with guard columns (NaN beside X: never read; a sentinel beside
+  // out: never written), against a double-precision loop within the summation-order bar
+  // (deg + 3) * 2^-24 * sum |term|
+  {
+    const int64_t ldx = F + 5, ldo = F + 3;
+    const float kGuard = -7.25f;
+    std::vector<float> Xs(n * ldx, std::nanf("")), os(n * ldo);
+    for (int64_t r = 0; r < n; ++r)
+      for (int64_t f = 0; f < F; ++f) Xs[r * ldx + f] = dZ[r * F + f];
+    pg_csr_t bw = bwd;
+    bw.ew = w_slot.data();
+    for (int mode : {0, 2}) {
+      std::fill(os.begin(), os.end(), kGuard);
+      CHECK(pg_spmm_sum_cpu(&bw, Xs.data(), ldx, F, mode, mode == 2 ? ptr.data() : nullptr, os.data(), ldo) == 0,
+            "transposed sum mode %d: %s", mode, pg_last_error_string());
+      for (int64_t r = 0; r < n; ++r) {
+        const int64_t d = tptr[r + 1] - tptr[r];
+        for (int64_t f = 0; f < F; ++f) {
+          double ref = 0.0, mag = 0.0;
+          for (int32_t k = tptr[r]; k < tptr[r + 1]; ++k) {
+            const int32_t c = tcol[k];
+            double t = (double)w_slot[tslot[k]] * (double)Xs[c * ldx + f];
+            if (mode == 2) t /= (double)(ptr[c + 1] - ptr[c]);
+            ref += t;
+            mag += std::fabs(t);
+          }
+          const double bar = (double)(d + 3) * 5.9604644775390625e-8 * mag + 1e-30;
+          CHECK(std::fabs((double)os[r * ldo + f] - ref) <= bar, "transposed sum mode %d (%ld, %ld) %g vs %g", mode,
+                (long)r, (long)f, os[r * ldo + f], ref);
+        }
+        for (int64_t f = F; f < ldo; ++f) CHECK(os[r * ldo + f] == kGuard, "guard column written (%ld, %ld)", (long)r, (long)f);
+      }
+    }
+    // the argument checks: nothing is read or written after an error
+    CHECK(pg_spmm_sum_cpu(&bw, Xs.data(), F - 1, F, 0, nullptr, os.data(), ldo) == PG_ERR_INVALID, "ldx < F");
+    CHECK(pg_spmm_sum_cpu(&bw, Xs.data(), ldx, F, 0, nullptr, os.data(), F - 1) == PG_ERR_INVALID, "ldo < F");
+    CHECK(pg_spmm_sum_cpu(&bw, Xs.data(), ldx, F, 3, ptr.data(), os.data(), ldo) == PG_ERR_INVALID, "norm_mode 3");
+    CHECK(pg_spmm_sum_cpu(&bw, Xs.data(), ldx, F, 2, nullptr, os.data(), ldo) == PG_ERR_INVALID, "mode 2, no norm_ptr");
+    CHECK(pg_spmm_sum_cpu(&bw, nullptr, ldx, F, 0, nullptr, os.data(), ldo) == PG_ERR_INVALID, "NULL X");
+    CHECK(pg_spmm_sum_cpu(&bw, Xs.data(), ldx, F, 0, nullptr, nullptr, ldo) == PG_ERR_INVALID, "NULL out");
+    CHECK(pg_spmm_sum_cpu(&bw, nullptr, ldx, 0, 0, nullptr, nullptr, ldo) == 0, "F = 0 touches no buffer");
   }
 }
 

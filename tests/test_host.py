@@ -121,6 +121,8 @@ def test_cpu_backend_max_bitexact(oracle_mod, F, weighted):
 
 def test_cpu_backend_sum_mean(oracle_mod):
     import plagnn
+    import sddmm_common
+    import sum_common
     from plagnn import ops
 
     src, dst = random_graph(80, 500, 3)
@@ -136,10 +138,15 @@ def test_cpu_backend_sum_mean(oracle_mod):
     for s, d in zip(src, dst):
         A[d, s] += 1
     deg = A.sum(1, keepdims=True)
-    dZ = np.random.default_rng(4).standard_normal((80, 7))
-    expect = (A / np.maximum(deg, 1)).T @ dZ
-    got = ops.spmm_sum(dg, torch.from_numpy(dZ.astype(np.float32)), mean=True, transpose=True)
-    np.testing.assert_allclose(got.numpy(), expect, rtol=1e-5, atol=1e-5)
+    dZ = np.random.default_rng(4).standard_normal((80, 7)).astype(np.float32)
+    expect = (A / np.maximum(deg, 1)).T @ dZ.astype(np.float64)
+    got = ops.spmm_sum(dg, torch.from_numpy(dZ), mean=True, transpose=True)
+    # the summation-order bar of tests/sum_common.py in place of rtol = atol = 1e-5; the dense
+    # product and the CSR reference are the same float64 sum up to its own rounding
+    ref, bar = sum_common.sum_ref64(g.bwd, dZ, None, 2, g.fwd.ptr)
+    np.testing.assert_allclose(ref, expect, rtol=0, atol=1e-13)
+    sddmm_common.assert_within(got, expect, bar, "transposed mean against the dense product")
+    assert (bar < 1e-5).all()
 
 
 def test_dgl_shim_surface_like_utils_create_graph():
