@@ -1,5 +1,5 @@
 """Per-kernel VGPR/AGPR/occupancy/scratch/LDS from hipcc -Rpass-analysis (gfx950).
-Usage: [RU_FLAGS=-DX=1] python scripts/resource_usage.py pla-gnn_amd/csrc/spmm.hip [filter]"""
+Usage: [RU_FLAGS=-DX=1] python scripts/resource_usage.py pla-gnn_amd/csrc/spmm_max_fwd.hip [filter]"""
 import os
 import re
 import subprocess

@@ -1,5 +1,6 @@
 #!/bin/bash
-# SpMM micro-benchmark over library variants (make variant V=... VSRC=spmm): gpurun_out/spmm_var.txt
+# SpMM micro-benchmark over library variants (make variant V=... VSRC="spmm_max_fwd spmm_max_bwd", or
+# whichever of spmm_sum, attention, gspmm holds the kernel under test); the results are appended to spmm_var.txt
 set -u
 mkdir -p gpurun_out
 for v in "" ${VARS:-}; do
