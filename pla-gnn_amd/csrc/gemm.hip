@@ -29,6 +29,12 @@
 // C[row = (r & 3) + 8 (r >> 2) + 4 (l >> 5)][col = l & 31] in register r.
 // Long-K products (weight gradients, K = number of nodes) use split-K with partial
 // slabs summed in a fixed order (deterministic).
+//
+// This file also holds the f32 entry points (pg_gemm_f32, _partials, _cat, _rows, _group,
+// pg_gemm_splitk_reduce_batch): they send a product to the three-piece kernels of
+// gemm_x3.hip where its operands allow (x3_ok), else to the kernels here. The host code the
+// GEMM families share (checks, K slicing, dispatch helpers, the combine launch, the grouped
+// launches' layout) is gemm_host.hpp; pick_tile and tile_built say which tiles are built.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -36,6 +42,7 @@
 
 #include "common.hpp"
 #include "gemm_common.hpp"
+#include "gemm_host.hpp"
 
 namespace {
 
@@ -61,17 +68,14 @@ constexpr int KPAD = BK + 4;  // [row][k] image row stride (floats)
 constexpr int kSplitBM = PG_SPLIT_TILE / 1000, kSplitBN = PG_SPLIT_TILE % 1000;
 //   PG_GEMM_ALGO       = 1: products whose operands allow 16-B loads run on the bf16 matrix
 //                        cores as three-piece splits (gemm_x3.hip), 0: f32 MFMA only;
-//   PG_X3_TILE_FORCE   = BM * 1000 + BN forces one tile of the three-piece kernel;
+//   PG_X3_TILE_FORCE   = BM * 1000 + BN forces one tile of the three-piece kernel
+//                        (gemm_host.hpp; build gemm_x3.hip with it too, or the tile is missing);
 //   PG_X3_SPLIT_TARGET = workgroups a split-K product of the three-piece kernel aims at.
 #ifndef PG_GEMM_ALGO
 #define PG_GEMM_ALGO 1
 #endif
-#ifndef PG_X3_TILE_FORCE
-#define PG_X3_TILE_FORCE 0
-#endif
 #ifndef PG_X3_GROUP_TARGET
-// workgroups of a grouped split-K launch: three 128 x 128 per CU, two 128 x 256 per CU
-#define PG_X3_GROUP_TARGET (kX3GroupBN > 128 ? 512 : 768)
+#define PG_X3_GROUP_TARGET 512  // workgroups of a grouped split-K launch: two 128 x 256 per CU
 #endif
 #ifndef PG_X3_MIN_SLICE
 #define PG_X3_MIN_SLICE 128  // shortest K slice of a split product of the three-piece kernel
@@ -354,9 +358,7 @@ __global__ __launch_bounds__(kThreads) void gemm_f32_kernel(
 
   // XCD-aware tile order: blocks b, b+8, ... share an XCD; give each such group a
   // contiguous run of tile ids (row-major over [tile_m][tile_n]).
-  const int b = blockIdx.x;
-  const int q8 = tiles / 8, r8 = tiles % 8, x8 = b % 8;
-  const int tile = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + b / 8;
+  const int tile = xcd_item(tiles);
   const int tm = tile / tiles_n, tn = tile % tiles_n;
 
   const int tid = threadIdx.x;
@@ -514,10 +516,7 @@ __global__ __launch_bounds__(kThreads) void gemm_dma_kernel(
   // an XCD and take a contiguous run of slice-major item ids, so an XCD holds whole
   // K-slices (every tile of a slice reads the same K rows of A and B: they meet in one L2)
   // and, without split, the column tiles of a row tile (their shared A rows)
-  const int b = blockIdx.x;
-  const int items = tiles * n_split;
-  const int q8 = items / 8, r8 = items % 8, x8 = b % 8;
-  const int item = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + b / 8;
+  const int item = xcd_item(tiles * n_split);
   const int kz = item / tiles, tile = item % tiles;
   const int tm = tile / tiles_n, tn = tile % tiles_n;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -642,63 +641,6 @@ struct Args {
   int vec_out;
 };
 
-template <int BM, int BN, bool TA, bool TB, bool VA, bool VB>
-int launch_epi(int epi, dim3 grid, hipStream_t st, const Args& a) {
-#define PG_L(EPI_)                                                                          \
-  hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, TA, TB, VA, VB, EPI_>), grid, dim3(kThreads), 0, \
-                     st, a.M, a.N, a.K, a.kps, a.tiles_n, a.tiles, a.alpha, a.A, a.lda, a.B,  \
-                     a.ldb, a.beta, a.C, a.ldc, a.bias, a.slope, a.dact, a.lddact, a.rowsum,  \
-                     a.ws, a.ws_rowsum)
-  switch (epi) {
-    case EPI_NONE: PG_L(EPI_NONE); break;
-    case EPI_RELU: PG_L(EPI_RELU); break;
-    case EPI_LEAKY: PG_L(EPI_LEAKY); break;
-    case EPI_DRELU: PG_L(EPI_DRELU); break;
-    case EPI_DLEAKY: PG_L(EPI_DLEAKY); break;
-    case EPI_SPLIT: PG_L(EPI_SPLIT); break;
-    default: return PG_ERR_INVALID;
-  }
-#undef PG_L
-  return PG_OK;
-}
-
-template <int BM, int BN, bool TA, bool TB>
-int launch_dma(int epi, dim3 grid, hipStream_t st, const Args& a) {
-#define PG_L(EPI_)                                                                          \
-  hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, TA, TB, EPI_>), dim3(grid.x * grid.z), dim3(kThreads), \
-                     0, st, a.M, a.N, a.K, a.kps, a.tiles_n, a.tiles, a.alpha, a.A, a.lda, a.B,  \
-                     a.ldb, a.beta, a.C, a.ldc, a.bias, a.slope, a.dact, a.lddact, a.rowsum,     \
-                     a.ws, a.ws_rowsum, a.vec_out, (int)grid.z)
-  switch (epi) {
-    case EPI_NONE: PG_L(EPI_NONE); break;
-    case EPI_RELU: PG_L(EPI_RELU); break;
-    case EPI_LEAKY: PG_L(EPI_LEAKY); break;
-    case EPI_DRELU: PG_L(EPI_DRELU); break;
-    case EPI_DLEAKY: PG_L(EPI_DLEAKY); break;
-    case EPI_SPLIT: PG_L(EPI_SPLIT); break;
-    default: return PG_ERR_INVALID;
-  }
-#undef PG_L
-  return PG_OK;
-}
-
-template <int BM, int BN, bool TA, bool TB>
-int launch_vec(bool va, bool vb, int epi, dim3 grid, hipStream_t st, const Args& a) {
-  if (va && vb) return launch_dma<BM, BN, TA, TB>(epi, grid, st, a);
-  if (va) return launch_epi<BM, BN, TA, TB, true, false>(epi, grid, st, a);
-  if (vb) return launch_epi<BM, BN, TA, TB, false, true>(epi, grid, st, a);
-  return launch_epi<BM, BN, TA, TB, false, false>(epi, grid, st, a);
-}
-
-template <int BM, int BN>
-int launch_trans(bool ta, bool tb, bool va, bool vb, int epi, dim3 grid, hipStream_t st,
-                 const Args& a) {
-  if (!ta && !tb) return launch_vec<BM, BN, false, false>(va, vb, epi, grid, st, a);
-  if (!ta && tb) return launch_vec<BM, BN, false, true>(va, vb, epi, grid, st, a);
-  if (ta && !tb) return launch_vec<BM, BN, true, false>(va, vb, epi, grid, st, a);
-  return launch_vec<BM, BN, true, true>(va, vb, epi, grid, st, a);
-}
-
 // Tile choice (measured on the PLA-GNN step shapes, scripts/gemm_bench.py): split-K
 // products (weight gradients) 64 x 64; outputs wider than 512 columns 128 x 128 when that
 // still gives >= 3 workgroups per CU, else 64 x 128; 129..512 columns with short K
@@ -724,31 +666,42 @@ inline void pick_tile(int64_t M, int64_t N, int64_t K, int split, int& bm, int& 
     bm = 128;
   }
 }
+// the tiles pick_tile can return: split products one, the others any of the four
+template <int BM, int BN>
+constexpr bool tile_built(bool split) {
+  if (PG_GEMM_TILE_FORCE != 0) return BM * 1000 + BN == PG_GEMM_TILE_FORCE;
+  return !split || (BM == kSplitBM && BN == kSplitBN);
+}
 
-// Tile of the three-piece kernel (measured per cfg2 shape with each tile forced, within 1-3 %
-// of the best everywhere): 128 x 128 (4 waves of 64 x 64: 0.5 fragment reads per MFMA)
-// wherever that gives >= 2 workgroups per CU; else 128 x 64, else 64 x 64. (Round 6: a
-// long-K product with 256-511 128 x 128 tiles, cfg2's fwd.cat.l1, runs 87.2 instead of 91.0
-// us on 128 x 64 tiles: 752 tiles share out over 256 CUs, 376 leave 136 CUs one tile idle.) Split products: 128 x 128, ~2 workgroups per CU (512: 1.636 ms/step, 768: 1.667,
-// 1024: 1.721).
-inline void pick_tile_x3(int64_t M, int64_t N, int64_t K, int split, int& bm, int& bn) {
-  if constexpr (PG_X3_TILE_FORCE != 0) {  // variant builds only
-    bm = PG_X3_TILE_FORCE / 1000;
-    bn = PG_X3_TILE_FORCE % 1000;
-    return;
-  }
-  auto tiles = [&](int tm, int tn) { return ((M + tm - 1) / tm) * ((N + tn - 1) / tn); };
-  if (split > 1) {
-    bm = M > 64 ? 128 : 64;
-    bn = N > 64 ? 128 : 64;
-    return;
-  }
-  bm = bn = 64;
-#ifndef PG_X3_LONGK_128
-#define PG_X3_LONGK_128 0  // 1: long-K products with 256-511 128 x 128 tiles keep 128 x 128
-#endif
-  if (tiles(128, 128) >= 512 || (PG_X3_LONGK_128 && tiles(128, 128) >= 256 && K >= 1000)) bm = bn = 128;
-  else if (tiles(128, 64) >= 512) bm = 128;
+// Launch on the picked tile: the LDS-DMA kernel when both operands allow 16-B loads (va,
+// vb), else the register-staged kernel with each operand's loader form.
+int launch(int bm, int bn, bool ta, bool tb, bool va, bool vb, int epi, int n_split, hipStream_t st, const Args& a) {
+  return dispatch_tile<Tile<128, 128>, Tile<64, 128>, Tile<128, 64>, Tile<64, 64>>(bm, bn, [&](auto tile) {
+    return dispatch_flags(ta, tb, [&](auto ta_, auto tb_) {
+      return dispatch_epi(epi, [&](auto epi_) {
+        return dispatch_flags(va, vb, [&](auto va_, auto vb_) {
+          constexpr int BM = decltype(tile)::bm, BN = decltype(tile)::bn, EPI = decltype(epi_)::value;
+          constexpr bool TA = decltype(ta_)::value, TB = decltype(tb_)::value;
+          constexpr bool VA = decltype(va_)::value, VB = decltype(vb_)::value;
+          if constexpr (!tile_built<BM, BN>(EPI == EPI_SPLIT)) {
+            return (int)PG_ERR_INVALID;
+          } else if constexpr (VA && VB) {
+            hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, TA, TB, EPI>), dim3(a.tiles * n_split), dim3(kThreads), 0, st,
+                               a.M, a.N, a.K, a.kps, a.tiles_n, a.tiles, a.alpha, a.A, a.lda, a.B, a.ldb, a.beta, a.C,
+                               a.ldc, a.bias, a.slope, a.dact, a.lddact, a.rowsum, a.ws, a.ws_rowsum, a.vec_out,
+                               n_split);
+            return (int)PG_OK;
+          } else {
+            hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, TA, TB, VA, VB, EPI>), dim3(a.tiles, 1, n_split),
+                               dim3(kThreads), 0, st, a.M, a.N, a.K, a.kps, a.tiles_n, a.tiles, a.alpha, a.A, a.lda,
+                               a.B, a.ldb, a.beta, a.C, a.ldc, a.bias, a.slope, a.dact, a.lddact, a.rowsum, a.ws,
+                               a.ws_rowsum);
+            return (int)PG_OK;
+          }
+        });
+      });
+    });
+  });
 }
 
 // the three-piece kernel takes the product: 16-B loads along every contiguous extent, and
@@ -813,21 +766,11 @@ int gemm_f32_impl(int transa, int transb, int64_t M, int64_t N, int64_t K, float
                   const float* A, int64_t lda, const float* B, int64_t ldb, float beta, float* C,
                   int64_t ldc, const pg_gemm_epilogue_t* ep, int split_k, void* ws,
                   size_t ws_bytes, pg_stream_t stream, bool defer, int* split_used) {
-  const pg_gemm_epilogue_t none{nullptr, PG_ACT_NONE, 0.f, nullptr, 0, nullptr};
-  if (!ep) ep = &none;
-  const int act = ep->act;
-  if (M < 0 || N < 0 || K < 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX)
-    return pg::set_error(PG_ERR_INVALID, "pg_gemm_f32: bad sizes");
-  if (ldc < N || (!transa && lda < K) || (transa && lda < M) || (!transb && ldb < N) ||
-      (transb && ldb < K))
-    return pg::set_error(PG_ERR_INVALID, "pg_gemm_f32: leading dimension too small");
-  if (act != PG_ACT_NONE && act != PG_ACT_RELU && act != PG_ACT_LEAKY)
-    return pg::set_error(PG_ERR_INVALID, "pg_gemm_f32: bad act %d", act);
+  if (!ep) ep = &kNoEpilogue;
   if (split_k < 1) split_k = 1;
-  if (split_k > 1 && (ep->bias || act != PG_ACT_NONE || ep->dact || (beta != 0.f && beta != 1.f)))
-    return pg::set_error(PG_ERR_INVALID, "pg_gemm_f32: split_k > 1 takes no bias/act, beta 0|1");
-  if (ep->dact && (act == PG_ACT_NONE || ep->lddact < N))
-    return pg::set_error(PG_ERR_INVALID, "pg_gemm_f32: dact needs act relu|leaky and lddact >= N");
+  if (const int rc = check_product("pg_gemm_f32", transa, transb, M, N, K, lda, ldb, ldc, *ep, beta, split_k, false,
+                                   "takes no bias/act, beta 0|1"))
+    return rc;
   if (M == 0 || N == 0) return pg::ok();
   if (split_k > 1 && ws_bytes < pg_gemm_f32_workspace(M, N, K, split_k))
     return pg::set_error(PG_ERR_WORKSPACE, "pg_gemm_f32: workspace too small");
@@ -835,69 +778,36 @@ int gemm_f32_impl(int transa, int transb, int64_t M, int64_t N, int64_t K, float
   // run's extent must be a multiple of 4 so no vector straddles the matrix edge
   const bool va = al16(A) && (lda % 4) == 0 && ((transa ? M : K) % 4) == 0;
   const bool vb = al16(B) && (ldb % 4) == 0 && ((transb ? K : N) % 4) == 0;
-  int kps = (int)K;
-  if (split_k > 1) {
-    kps = (int)((K + split_k - 1) / split_k);
-    kps = (kps + BK - 1) / BK * BK;
-    split_k = (int)((K + kps - 1) / kps);
-    if (split_k < 1) split_k = 1;
-  }
+  const int kps = k_slices(K, BK, split_k);
   const bool split = split_k > 1;
   if (split_used) *split_used = split_k;
   if (defer && !split) return pg::set_error(PG_ERR_INVALID, "pg_gemm_f32_partials: needs split_k > 1");
   hipStream_t st = (hipStream_t)stream;
   float* wsf = split ? (float*)ws : nullptr;
   float* ws_rs = split ? wsf + (int64_t)split_k * M * N : nullptr;  // row-sum slices after the slabs
-  const int epi = split ? EPI_SPLIT
-                        : ep->dact ? (act == PG_ACT_RELU ? EPI_DRELU : EPI_DLEAKY)
-                                   : (act == PG_ACT_RELU ? EPI_RELU : act == PG_ACT_LEAKY ? EPI_LEAKY : EPI_NONE);
-  int bm, bn;
+  const int epi = epi_code(*ep, split);
+  int bm, bn, tiles_n, tiles;
   int rc;
   if (x3_ok(transa, transb, M, N, K, A, lda, B, ldb, C, ldc, ep, split, ws)) {
     pick_tile_x3(M, N, K, split_k, bm, bn);
-    const int tiles_n = (int)((N + bn - 1) / bn);
-    const int tiles = tiles_n * (int)((M + bm - 1) / bm);
+    tile_grid(M, N, bm, bn, tiles_n, tiles);
     const X3Args xa{transa != 0, transb != 0, bm, bn, epi, (int)M, (int)N, (int)K, kps, tiles_n, tiles,
                     split_k, alpha, A, lda, B, ldb, beta, C, ldc, ep->bias, ep->slope, ep->dact,
                     ep->lddact, ep->rowsum, wsf, ws_rs};
     rc = gemm_x3_launch(xa, st);
   } else {
     pick_tile(M, N, K, split_k, bm, bn);
-    const int tiles_n = (int)((N + bn - 1) / bn);
-    const int tiles = tiles_n * (int)((M + bm - 1) / bm);
-    dim3 grid((unsigned)tiles, 1, (unsigned)split_k);
+    tile_grid(M, N, bm, bn, tiles_n, tiles);
     // 16-B epilogue stores (finish_tile_lds) when every output-side operand allows them
     const bool vec_out = (N % 4) == 0 && (split ? al16(wsf) : (al16(C) && (ldc % 4) == 0)) &&
                          (!ep->bias || al16(ep->bias)) &&
                          (!ep->dact || (al16(ep->dact) && (ep->lddact % 4) == 0));
     const Args a{(int)M, (int)N, (int)K, kps, tiles_n, tiles, alpha, A, lda, B, ldb, beta, C, ldc,
                  ep->bias, ep->slope, ep->dact, ep->lddact, ep->rowsum, wsf, ws_rs, vec_out ? 1 : 0};
-    const bool ta = transa != 0, tb = transb != 0;
-    if (bm == 128 && bn == 128)
-      rc = launch_trans<128, 128>(ta, tb, va, vb, epi, grid, st, a);
-    else if (bm == 64 && bn == 128)
-      rc = launch_trans<64, 128>(ta, tb, va, vb, epi, grid, st, a);
-    else if (bm == 128)
-      rc = launch_trans<128, 64>(ta, tb, va, vb, epi, grid, st, a);
-    else
-      rc = launch_trans<64, 64>(ta, tb, va, vb, epi, grid, st, a);
+    rc = launch(bm, bn, transa != 0, transb != 0, va, vb, epi, split_k, st, a);
   }
   if (rc != PG_OK) return pg::set_error(rc, "pg_gemm_f32: dispatch failed");
-  if (split && !defer) {
-    const int64_t n = (N % 4 == 0 ? M * N / 4 : M * N) + (ep->rowsum ? M : 0);  // work units
-    // threads per output: enough slice groups that each thread sums <= ~8 slices
-    const int G = splitk_groups(split_k);
-    const int opb = 256 / G;
-    const int blocks = (int)std::min<int64_t>(8192, (n + opb - 1) / opb);
-#define PG_R(G_)                                                                              \
-  hipLaunchKernelGGL(splitk_reduce_kernel<G_>, dim3(blocks), dim3(256), 0, st, (const float*)wsf, \
-                     split_k, (int)M, (int)N, alpha, beta, C, ldc, (const float*)ws_rs,          \
-                     ep->rowsum)
-    if (G == 1) PG_R(1);
-    else if (G == 4) PG_R(4);
-    else PG_R(16);
-#undef PG_R
-  }
+  if (split && !defer) launch_combine(wsf, split_k, M, N, alpha, beta, C, ldc, ws_rs, ep->rowsum, st);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess)
     return pg::set_error((int)e, "pg_gemm_f32: launch failed: %s", hipGetErrorString(e));
@@ -936,8 +846,7 @@ int pg_gemm_f32_cat(int transb, int64_t M, int64_t N, int64_t K1, int64_t K2, fl
                     int64_t lda1, const float* A2, int64_t lda2, const float* B1, int64_t ldb1, const float* B2,
                     int64_t ldb2, float beta, float* C, int64_t ldc, const pg_gemm_epilogue_t* ep,
                     pg_stream_t stream) {
-  const pg_gemm_epilogue_t none{nullptr, PG_ACT_NONE, 0.f, nullptr, 0, nullptr};
-  if (!ep) ep = &none;
+  if (!ep) ep = &kNoEpilogue;
   const int64_t K = K1 + K2;
   if (M < 0 || N < 0 || K1 < 0 || K2 < 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX)
     return pg::set_error(PG_ERR_INVALID, "pg_gemm_f32_cat: bad sizes");
@@ -953,12 +862,10 @@ int pg_gemm_f32_cat(int transb, int64_t M, int64_t N, int64_t K1, int64_t K2, fl
       !x3_ok(0, transb, M, N, K2, A2, lda2, B2, ldb2, C, ldc, ep, false, nullptr))
     return pg::set_error(PG_ERR_UNSUPPORTED,
                          "pg_gemm_f32_cat: needs K1 %% 4 == 0 and operands the three-piece kernel takes");
-  int bm, bn;
+  int bm, bn, tiles_n, tiles;
   pick_tile_x3(M, N, K, 1, bm, bn);
-  const int tiles_n = (int)((N + bn - 1) / bn);
-  const int tiles = tiles_n * (int)((M + bm - 1) / bm);
-  const int epi = ep->act == PG_ACT_LEAKY ? EPI_LEAKY : EPI_NONE;
-  const X3Args xa{false, transb != 0, bm, bn, epi, (int)M, (int)N, (int)K, (int)K, tiles_n, tiles, 1, alpha, A1,
+  tile_grid(M, N, bm, bn, tiles_n, tiles);
+  const X3Args xa{false, transb != 0, bm, bn, epi_code(*ep, false), (int)M, (int)N, (int)K, (int)K, tiles_n, tiles, 1, alpha, A1,
                   lda1, B1, ldb1, beta, C, ldc, ep->bias, ep->slope, nullptr, 0, nullptr, nullptr, nullptr};
   const int rc = gemm_x3_cat_launch(xa, A2, lda2, B2, ldb2, (int)K1, (hipStream_t)stream);
   const hipError_t e = hipGetLastError();
@@ -970,7 +877,6 @@ int pg_gemm_f32_cat(int transb, int64_t M, int64_t N, int64_t K1, int64_t K2, fl
 int pg_gemm_f32_rows(int transb, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda,
                      const float* B, int64_t ldb, float* C, int64_t ldc, const int32_t* rows,
                      int64_t n_rows, pg_stream_t stream) {
-  const pg_gemm_epilogue_t none{nullptr, PG_ACT_NONE, 0.f, nullptr, 0, nullptr};
   if (M < 0 || N < 0 || K < 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX || n_rows < 0 || n_rows > M)
     return pg::set_error(PG_ERR_INVALID, "pg_gemm_f32_rows: bad sizes");
   if (ldc < N || lda < K || (transb ? ldb < K : ldb < N))
@@ -978,12 +884,11 @@ int pg_gemm_f32_rows(int transb, int64_t M, int64_t N, int64_t K, const float* A
   if (n_rows == 0 || N == 0) return pg::ok();
   if (!rows || !A || !B || !C) return pg::set_error(PG_ERR_INVALID, "pg_gemm_f32_rows: NULL buffer");
   // (C's rows are reached by 64-bit addresses; A's by the 32-bit offsets x3_ok bounds)
-  if (K == 0 || !x3_ok(0, transb, M, N, K, A, lda, B, ldb, C, ldc, &none, false, nullptr))
+  if (K == 0 || !x3_ok(0, transb, M, N, K, A, lda, B, ldb, C, ldc, &kNoEpilogue, false, nullptr))
     return pg::set_error(PG_ERR_UNSUPPORTED, "pg_gemm_f32_rows: needs operands the three-piece kernel takes");
-  int bm, bn;
+  int bm, bn, tiles_n, tiles;
   pick_tile_x3(n_rows, N, K, 1, bm, bn);
-  const int tiles_n = (int)((N + bn - 1) / bn);
-  const int tiles = tiles_n * (int)((n_rows + bm - 1) / bm);
+  tile_grid(n_rows, N, bm, bn, tiles_n, tiles);
   const X3Args xa{false, transb != 0, bm, bn, EPI_NONE, (int)n_rows, (int)N, (int)K, (int)K, tiles_n, tiles, 1, 1.f, A,
                   lda, B, ldb, 0.f, C, ldc, nullptr, 0.f, nullptr, 0, nullptr, nullptr, nullptr};
   const int rc = gemm_x3_rows_launch(xa, rows, (int)M, (hipStream_t)stream);
@@ -1025,9 +930,7 @@ int pg_gemm_splitk_reduce_batch(const pg_splitk_job_t* jobs, int n_jobs, pg_stre
     a.job[k] = j;
     a.G[k] = splitk_groups(j.split_k);
     a.first_block[k] = blocks;
-    const int64_t n = (j.N % 4 == 0 ? j.M * j.N / 4 : j.M * j.N) + (j.rowsum ? j.M : 0);  // work units
-    const int opb = 256 / a.G[k];
-    blocks += (int)std::min<int64_t>(8192, (n + opb - 1) / opb);
+    blocks += combine_blocks(j.M, j.N, j.rowsum != nullptr, a.G[k]);
   }
   a.first_block[n_jobs] = blocks;
   hipLaunchKernelGGL(splitk_reduce_batch_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, a);
@@ -1041,42 +944,19 @@ int pg_gemm_splitk_reduce_batch(const pg_splitk_job_t* jobs, int n_jobs, pg_stre
 
 namespace {
 
-// The group's plan: one K-slice count for every part, chosen so that the union of the
-// parts' 128 x 128 tiles times the slices fills PG_X3_GROUP_TARGET workgroups (three per
-// CU), each slice >= PG_X3_MIN_SLICE entries of K; each part's slabs (+ row-sum slices) at
-// a 256-B aligned offset of ws.
-struct GroupPlan {
-  int split[kX3MaxParts];
-  int kps[kX3MaxParts];
-  size_t off[kX3MaxParts + 1];
-};
-
+// The group's slice-count policy: one K-slice count for every part, chosen so that the
+// union of the parts' 128 x 256 tiles times the slices fills PG_X3_GROUP_TARGET workgroups
+// (two per CU), each slice >= PG_X3_MIN_SLICE entries of K.
 inline void group_plan(const pg_gemm_part_t* parts, int n, GroupPlan& g) {
   int64_t tiles = 0;
   for (int p = 0; p < n; ++p)
     tiles += ((parts[p].M + kX3GroupBM - 1) / kX3GroupBM) * ((parts[p].N + kX3GroupBN - 1) / kX3GroupBN);
   const int64_t s = std::max<int64_t>(1, PG_X3_GROUP_TARGET / std::max<int64_t>(1, tiles));
-  size_t off = 0;
   for (int p = 0; p < n; ++p) {
-    const pg_gemm_part_t& q = parts[p];
-    int64_t sp = std::max<int64_t>(1, std::min<int64_t>(s, q.K / PG_X3_MIN_SLICE));
-    int64_t kps = (q.K + sp - 1) / sp;
-    kps = std::max<int64_t>(BK, (kps + BK - 1) / BK * BK);
-    sp = std::max<int64_t>(1, (q.K + kps - 1) / kps);
-    g.split[p] = (int)sp;
-    g.kps[p] = (int)kps;
-    g.off[p] = off;
-    off += ((size_t)sp * (size_t)std::max<int64_t>(q.M, 0) * (size_t)(std::max<int64_t>(q.N, 0) + 1) * 4 + 255) /
-           256 * 256;
+    g.in[p] = true;
+    g.split[p] = (int)std::max<int64_t>(1, std::min<int64_t>(s, parts[p].K / PG_X3_MIN_SLICE));
   }
-  g.off[n] = off;
-}
-
-inline bool part_ok(const pg_gemm_part_t& q) {
-  const bool bufs = (q.M == 0 || q.N == 0 || q.C) && (q.M == 0 || q.N == 0 || q.K == 0 || (q.A && q.B));
-  return bufs && q.M >= 0 && q.N >= 0 && q.K >= 0 && q.M <= INT32_MAX && q.N <= INT32_MAX && q.K <= INT32_MAX &&
-         q.ldc >= q.N && (q.transa ? q.lda >= q.M : q.lda >= q.K) && (q.transb ? q.ldb >= q.K : q.ldb >= q.N) &&
-         (q.beta == 0.f || q.beta == 1.f);
+  group_layout(parts, n, BK, g);
 }
 
 }  // namespace
@@ -1084,7 +964,7 @@ inline bool part_ok(const pg_gemm_part_t& q) {
 extern "C" {
 
 size_t pg_gemm_f32_group_workspace(const pg_gemm_part_t* parts, int n) {
-  if (n <= 0 || n > kX3MaxParts || !parts) return 0;
+  if (n <= 0 || n > kMaxParts || !parts) return 0;
   GroupPlan g;
   group_plan(parts, n, g);
   size_t need = g.off[n];
@@ -1096,8 +976,8 @@ size_t pg_gemm_f32_group_workspace(const pg_gemm_part_t* parts, int n) {
 }
 
 int pg_gemm_f32_group(const pg_gemm_part_t* parts, int n, void* ws, size_t ws_bytes, pg_stream_t stream) {
-  if (n < 0 || n > kX3MaxParts || (n > 0 && !parts))
-    return pg::set_error(PG_ERR_INVALID, "pg_gemm_f32_group: 0..%d parts", kX3MaxParts);
+  if (n < 0 || n > kMaxParts || (n > 0 && !parts))
+    return pg::set_error(PG_ERR_INVALID, "pg_gemm_f32_group: 0..%d parts", kMaxParts);
   if (n == 0) return pg::ok();
   for (int p = 0; p < n; ++p)
     if (!part_ok(parts[p])) return pg::set_error(PG_ERR_INVALID, "pg_gemm_f32_group: bad part %d", p);
@@ -1105,12 +985,11 @@ int pg_gemm_f32_group(const pg_gemm_part_t* parts, int n, void* ws, size_t ws_by
     return pg::set_error(PG_ERR_WORKSPACE, "pg_gemm_f32_group: workspace too small");
   GroupPlan g;
   group_plan(parts, n, g);
-  const pg_gemm_epilogue_t none{nullptr, PG_ACT_NONE, 0.f, nullptr, 0, nullptr};
   bool grouped = PG_GEMM_ALGO != 0;
   for (int p = 0; p < n && grouped; ++p) {
     const pg_gemm_part_t& q = parts[p];
     grouped = q.transa == parts[0].transa && q.transb == parts[0].transb &&
-              x3_ok(q.transa, q.transb, q.M, q.N, q.K, (const float*)q.A, q.lda, (const float*)q.B, q.ldb, nullptr, 0, &none, true,
+              x3_ok(q.transa, q.transb, q.M, q.N, q.K, (const float*)q.A, q.lda, (const float*)q.B, q.ldb, nullptr, 0, &kNoEpilogue, true,
                     (char*)ws + g.off[p]);
   }
   if (!grouped) {  // each part on its own (split-K product + combine)
@@ -1125,30 +1004,9 @@ int pg_gemm_f32_group(const pg_gemm_part_t* parts, int n, void* ws, size_t ws_by
     return pg::ok();
   }
   X3Group xg{};
-  pg_splitk_job_t jobs[kX3MaxParts];
-  int items = 0, nj = 0;
-  for (int p = 0; p < n; ++p) {
-    const pg_gemm_part_t& q = parts[p];
-    if (q.M == 0 || q.N == 0) continue;
-    float* w = (float*)((char*)ws + g.off[p]);
-    X3Part& x = xg.p[nj];
-    x.M = (int)q.M; x.N = (int)q.N; x.K = (int)q.K; x.kps = g.kps[p];
-    x.tiles_n = (int)((q.N + kX3GroupBN - 1) / kX3GroupBN);
-    x.tiles = x.tiles_n * (int)((q.M + kX3GroupBM - 1) / kX3GroupBM);
-    x.first_item = items;
-    x.A = (const float*)q.A; x.lda = q.lda; x.B = (const float*)q.B; x.ldb = q.ldb;
-    x.ws = w;
-    x.ws_rowsum = w + (int64_t)g.split[p] * q.M * q.N;
-    x.rowsum = q.rowsum;
-    items += x.tiles * g.split[p];
-    pg_splitk_job_t& j = jobs[nj];
-    j.ws = w; j.split_k = g.split[p]; j.M = q.M; j.N = q.N;
-    j.alpha = 1.f; j.beta = q.beta; j.C = q.C; j.ldc = q.ldc; j.rowsum = q.rowsum;
-    ++nj;
-  }
+  pg_splitk_job_t jobs[kMaxParts];
+  const int nj = group_fill(parts, n, g, kX3GroupBM, kX3GroupBN, ws, xg, jobs);
   if (nj == 0) return pg::ok();
-  xg.n = nj;
-  xg.items = items;
   const int rc = gemm_x3_group_launch(xg, parts[0].transa != 0, parts[0].transb != 0, (hipStream_t)stream);
   const hipError_t e = hipGetLastError();
   if (rc != PG_OK || e != hipSuccess)

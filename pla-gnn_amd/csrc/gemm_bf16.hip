@@ -5,9 +5,12 @@
 // are stored as bf16, weights are bf16 copies of the f32 master parameters, every
 // product accumulates in f32, weight gradients leave in f32.
 //
-// Tiling: BM x BN per 256-thread workgroup (BM, BN in {64, 128}); 2 x 2 waves, each
-// owning (BM/2) x (BN/2) = TM x TN MFMA tiles of 32 x 32; K step 64 (four MFMA k-steps of
-// 16). K tiles go global -> LDS by LDS-DMA (global_load_lds_dwordx4, no register round
+// Tiling: 64 x 64, 128 x 64 and 128 x 128 per 256-thread workgroup (2 x 2 waves) and
+// 256 x 256 per 512-thread workgroup (2 x 4 waves), each wave owning TM x TN MFMA tiles of
+// 32 x 32; K step 64 (four MFMA k-steps of 16). A B^T on 256 x 256 tiles has a kernel of its
+// own (the ping-pong kernel below). The host side (argument checks, K slicing, dispatch, the
+// grouped launch's plan) is built from gemm_host.hpp; pick_tile and tile_built say which
+// tiles exist. K tiles go global -> LDS by LDS-DMA (global_load_lds_dwordx4, no register round
 // trip) into two images per operand; the tile for step t+1 is issued at the top of step
 // t and waited for by the step's single barrier. Fragments for k-step s+1 are read while
 // the MFMAs of k-step s run (across K steps too), as in the fp32 kernel.
@@ -41,44 +44,31 @@
 
 #include "common.hpp"
 #include "gemm_common.hpp"
+#include "gemm_host.hpp"
 
 namespace {
 
 using namespace pg_gemm;
 
-constexpr int BK = 64;  // bf16 k-values per K step (two-stage kernels; deep ones use 32)
-#ifndef PG_BF16_WM  // wave grid of the 256 x 256 tile: 2 x 4 = eight waves, two per SIMD (measured
-                    // +9 ... +25 % over 2 x 2 on the cfg5 shapes: the second wave of a SIMD issues
-                    // its LDS reads and DMA while the first one runs MFMAs)
-#define PG_BF16_WM 2
-#endif
-#ifndef PG_BF16_WN
-#define PG_BF16_WN 4
-#endif
-#ifndef PG_BF16_DEEP
-#define PG_BF16_DEEP 0
-#endif
-#ifndef PG_BF16_T2  // variant builds: 256 x 128 tiles, KB = 32, two workgroups per CU
-#define PG_BF16_T2 0
-#endif
-#ifndef PG_BF16_T2_NS
-#define PG_BF16_T2_NS 2
-#endif
+constexpr int BK = 64;  // bf16 k-values per K step
+constexpr int NS = 2;   // LDS stages per operand
+// wave grid of the 256 x 256 tile: 2 x 4 = eight waves, two per SIMD (measured +9 ... +25 %
+// over 2 x 2 on the cfg5 shapes: the second wave of a SIMD issues its LDS reads and DMA while
+// the first one runs MFMAs); every other tile 2 x 2
+constexpr int kBigWM = 2, kBigWN = 4;
 
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using lds_bf16x4 = __attribute__((address_space(3))) bf16x4;
 
-// element offset (u16 units) of (row, k) in an image of KB k-values per row. Row images:
-// 128-B rows (KB = 64) swizzle chunk c to c ^ ((row >> 1) & 7), 64-B rows (KB = 32) to
-// c ^ ((row >> 2) & 3): either way 16 consecutive rows at one chunk hit 16 distinct bank
-// quads for ds_read_b128.
-template <int ROWS, bool KMAJ, int KB = BK>
+// element offset (u16 units) of (row, k) in an image of BK k-values per row. Row images
+// (128-B rows) swizzle chunk c to c ^ ((row >> 1) & 7): 16 consecutive rows at one chunk hit
+// 16 distinct bank quads for ds_read_b128.
+template <int ROWS, bool KMAJ>
 __device__ __forceinline__ int img_off(int row, int k) {
   if constexpr (!KMAJ) {
-    if constexpr (KB == 64) return row * KB + ((((k >> 3) ^ ((row >> 1) & 7))) << 3) + (k & 7);
-    else return row * KB + ((((k >> 3) ^ ((row >> 2) & 3))) << 3) + (k & 7);
+    return row * BK + ((((k >> 3) ^ ((row >> 1) & 7))) << 3) + (k & 7);
   } else {
     const int f = ROWS == 64 ? ((k >> 1) & 1) * 4 : (k & 3) * 4;
     return k * ROWS + ((((row >> 3) ^ f)) << 3) + (row & 7);
@@ -87,10 +77,10 @@ __device__ __forceinline__ int img_off(int row, int k) {
 
 // DMA of one ROWS x BK tile (rows [r0, r0 + ROWS) x k [k0, k0 + BK)) into an image;
 // units past K (kvalid) are zero-filled by the lane that owns them.
-template <int ROWS, bool KMAJ, bool FULL, int NW, int KB = BK>
+template <int ROWS, bool KMAJ, bool FULL, int NW>
 __device__ __forceinline__ void dma_tile(const uint16_t* __restrict__ P, int64_t ld, int r0, int R,
                                          int k0, int kvalid, uint16_t* S, int wave, int lane) {
-  constexpr int PIECES = ROWS * KB * 2 / 1024;  // 1-KiB pieces of the image
+  constexpr int PIECES = ROWS * BK * 2 / 1024;  // 1-KiB pieces of the image
   static_assert(PIECES % NW == 0, "image pieces per wave");
 #pragma unroll
   for (int j = 0; j < PIECES / NW; ++j) {
@@ -99,9 +89,9 @@ __device__ __forceinline__ void dma_tile(const uint16_t* __restrict__ P, int64_t
     const uint16_t* src;
     bool valid;
     if constexpr (!KMAJ) {
-      constexpr int UPR = KB / 8;  // units per row
+      constexpr int UPR = BK / 8;  // units per row
       const int row = u / UPR;
-      const int c = KB == 64 ? ((u & 7) ^ ((row >> 1) & 7)) : ((u & 3) ^ ((row >> 2) & 3));
+      const int c = (u & 7) ^ ((row >> 1) & 7);
       valid = 8 * c < kvalid;
       src = P + (int64_t)min(r0 + row, R - 1) * ld + k0 + 8 * c;
     } else {
@@ -118,11 +108,11 @@ __device__ __forceinline__ void dma_tile(const uint16_t* __restrict__ P, int64_t
 }
 
 // the 8 k-values of k-step s for MFMA row/col `rc` (tile-local) of lane half h
-template <int ROWS, bool KMAJ, int KB = BK>
+template <int ROWS, bool KMAJ>
 __device__ __forceinline__ bf16x8 frag(const uint16_t* __restrict__ S, int rc, int s, int lane) {
   if constexpr (!KMAJ) {
     const int h = lane >> 5;
-    return *reinterpret_cast<const bf16x8*>(S + img_off<ROWS, false, KB>(rc, 16 * s + 8 * h));
+    return *reinterpret_cast<const bf16x8*>(S + img_off<ROWS, false>(rc, 16 * s + 8 * h));
   } else {
     // ds_read_b64_tr_b16: lane 4q + p of a 16-lane group supplies the address of block row
     // q (k), columns 4p .. 4p + 3 (rows of the operand); the group's block is k-rows
@@ -132,9 +122,9 @@ __device__ __forceinline__ bf16x8 frag(const uint16_t* __restrict__ S, int rc, i
     const int m = rc - (lane & 15) + 4 * p;
     const int kb = 16 * s + 8 * (g >> 1);
     const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-        (lds_bf16x4*)(S + img_off<ROWS, true, KB>(m, kb + q)));
+        (lds_bf16x4*)(S + img_off<ROWS, true>(m, kb + q)));
     const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16(
-        (lds_bf16x4*)(S + img_off<ROWS, true, KB>(m, kb + 4 + q)));
+        (lds_bf16x4*)(S + img_off<ROWS, true>(m, kb + 4 + q)));
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
   }
 }
@@ -147,26 +137,26 @@ __device__ __forceinline__ uint16_t f2bf(float x) {
 }
 
 // row sums of the A tile in LDS over its BK k-values (thread t: row t % BM, k-group t / BM)
-template <int BM, bool AK, int NT, int KB = BK>
+template <int BM, bool AK, int NT>
 __device__ __forceinline__ float img_rowsum(const uint16_t* __restrict__ As, int tid) {
   constexpr int G = NT / BM;
   const int m = tid % BM, g = tid / BM;
   float s = 0.f;
 #pragma unroll
-  for (int i = 0; i < KB / G; ++i) s += bf2f(As[img_off<BM, AK, KB>(m, g + i * G)]);
+  for (int i = 0; i < BK / G; ++i) s += bf2f(As[img_off<BM, AK>(m, g + i * G)]);
   return s;
 }
 
-// row sums of a k-image A tile ([KB k][BM rows], 8-row chunks swizzled per k-row): thread t
+// row sums of a k-image A tile ([BK k][BM rows], 8-row chunks swizzled per k-row): thread t
 // adds chunk t % (BM / 8)'s 8 rows over the k-rows t / (BM / 8) + G i with one
 // ds_read_b128 each (8x fewer LDS reads than one u16 per row and k)
-template <int BM, int NT, int KB = BK>
+template <int BM, int NT>
 __device__ __forceinline__ void img_rowsum8(const uint16_t* __restrict__ As, int tid, float (&rs)[8]) {
   constexpr int CPR = BM / 8, G = NT / CPR;
-  static_assert(NT % CPR == 0 && KB % G == 0, "k-groups");
+  static_assert(NT % CPR == 0 && BK % G == 0, "k-groups");
   const int c = tid % CPR, g = tid / CPR;
 #pragma unroll
-  for (int i = 0; i < KB / G; ++i) {
+  for (int i = 0; i < BK / G; ++i) {
     const int k = g + i * G;
     const int f = BM == 64 ? ((k >> 1) & 1) * 4 : (k & 3) * 4;
     const uint4 v = *reinterpret_cast<const uint4*>(As + k * BM + ((c ^ f) << 3));
@@ -320,22 +310,18 @@ __device__ __forceinline__ void finish_tile(const f32x16 (&acc)[BM / WM / 32][BN
   }
 }
 
-// KB k-values per stage, NS LDS stages. NS = 2: the tile for step t+1 is issued at the top
-// of step t and waited for by __syncthreads. NS > 2 (the 256 x 256 tiles, one workgroup per
-// CU, where nothing else hides the DMA latency): NS - 1 tiles in flight; each step waits for
-// the next tile only with a counted s_waitcnt vmcnt (the later tiles stay in flight) and a
-// raw s_barrier (cdna_hip_programming.md "Pipelining across barriers"); a partial last K
-// tile (fewer DMAs) switches the count to 0.
-template <int BM, int BN, int WM, int WN, int KB, int NS>
+// NS = 2 LDS stages of BK k-values per operand: the tile for step t + 1 is issued at the top
+// of step t and waited for by the step's __syncthreads.
+template <int BM, int BN, int WM, int WN>
 constexpr int bf16_lds_u16() {
-  constexpr int STAGE = NS * (BM * KB + BN * KB);
+  constexpr int STAGE = NS * (BM * BK + BN * BK);
   constexpr int PASSES = 2 * BM * BN > STAGE ? WM : 1;
   constexpr int EPI_U16 = 2 * BM * BN / PASSES;
   return STAGE > EPI_U16 ? STAGE : EPI_U16;
 }
 
 // One output tile (tm, tn) over the K slice kz of the product: the whole workgroup's work.
-template <int BM, int BN, int WM, int WN, int KB, int NS, bool TA, bool TB, int EPI, bool OBF>
+template <int BM, int BN, int WM, int WN, bool TA, bool TB, int EPI, bool OBF>
 __device__ __forceinline__ void bf16_tile(
     uint16_t* __restrict__ lds, int M, int N, int K, int k_per_split, int kz, int tm, int tn, float alpha,
     const uint16_t* __restrict__ A, int64_t lda, const uint16_t* __restrict__ B, int64_t ldb,
@@ -345,9 +331,8 @@ __device__ __forceinline__ void bf16_tile(
   constexpr bool AK = TA, BKM = !TB;  // k images for A stored [k][m] / B stored [k][n]
   constexpr int NW = WM * WN, NT = 64 * NW;
   constexpr int TM = BM / WM / 32, TN = BN / WN / 32;  // 32 x 32 MFMA tiles per wave
-  constexpr int IA = BM * KB, IB = BN * KB;  // image sizes (u16)
-  constexpr int SS = KB / 16;                // MFMA k-steps per stage
-  constexpr int D = (BM + BN) * KB * 2 / 1024 / NW;  // DMA instructions per tile and wave
+  constexpr int IA = BM * BK, IB = BN * BK;  // image sizes (u16)
+  constexpr int SS = BK / 16;                // MFMA k-steps per stage
   static_assert(SS >= 2 && SS % 2 == 0, "an even number (>= 2) of MFMA k-steps per stage");
   // one LDS array [A0 .. A(NS-1) | B0 .. B(NS-1)]; the epilogue reuses it as a row-major f32
   // image of the tile (in WM row bands when the whole tile does not fit)
@@ -370,64 +355,45 @@ __device__ __forceinline__ void bf16_tile(
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  const int nk = kz1 > kz0 ? (kz1 - kz0 + KB - 1) / KB : 0;
-  const bool tail = ((kz1 - kz0) % KB) != 0;  // the last tile is partial (fewer DMAs)
+  const int nk = kz1 > kz0 ? (kz1 - kz0 + BK - 1) / BK : 0;
   auto issue = [&](int t, int buf) {
-    const int k0 = kz0 + t * KB;
-    if (kz1 - k0 >= KB) {
-      dma_tile<BM, AK, true, NW, KB>(A, lda, m0, M, k0, KB, lds + buf * IA, wave, lane);
-      dma_tile<BN, BKM, true, NW, KB>(B, ldb, n0, N, k0, KB, lds + NS * IA + buf * IB, wave, lane);
+    const int k0 = kz0 + t * BK;
+    if (kz1 - k0 >= BK) {
+      dma_tile<BM, AK, true, NW>(A, lda, m0, M, k0, BK, lds + buf * IA, wave, lane);
+      dma_tile<BN, BKM, true, NW>(B, ldb, n0, N, k0, BK, lds + NS * IA + buf * IB, wave, lane);
     } else {
-      dma_tile<BM, AK, false, NW, KB>(A, lda, m0, M, k0, kz1 - k0, lds + buf * IA, wave, lane);
-      dma_tile<BN, BKM, false, NW, KB>(B, ldb, n0, N, k0, kz1 - k0, lds + NS * IA + buf * IB, wave, lane);
-    }
-  };
-  // wait until tile `need` has landed (all waves), given tiles up to `last` issued
-  auto sync_tile = [&](int need, int last) {
-    if constexpr (NS == 2) {
-      __syncthreads();
-    } else {
-      const int after = last - need;  // tiles issued after `need`, still allowed in flight
-      if (after <= 0 || (tail && last == nk - 1)) wait_vmcnt<0>();
-      else if (after == 1) wait_vmcnt<D>();
-      else wait_vmcnt<2 * D>();
-      static_assert(NS <= 4, "vmcnt cases");
-      __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's LDS stores (zero fill)
-      __builtin_amdgcn_s_barrier();
+      dma_tile<BM, AK, false, NW>(A, lda, m0, M, k0, kz1 - k0, lds + buf * IA, wave, lane);
+      dma_tile<BN, BKM, false, NW>(B, ldb, n0, N, k0, kz1 - k0, lds + NS * IA + buf * IB, wave, lane);
     }
   };
 
   if (nk > 0) {
-    int issued = -1;
-    for (int p = 0; p < NS - 1 && p < nk; ++p) issue(p, p), issued = p;
-    sync_tile(0, issued);
+    for (int p = 0; p < NS - 1 && p < nk; ++p) issue(p, p);
+    __syncthreads();
     const int ra = wm * (BM / WM) + l32, rb = wn * (BN / WN) + l32;
     bf16x8 fa[2][TM], fb[2][TN];
 #pragma unroll
-    for (int i = 0; i < TM; ++i) fa[0][i] = frag<BM, AK, KB>(lds, ra + i * 32, 0, lane);
+    for (int i = 0; i < TM; ++i) fa[0][i] = frag<BM, AK>(lds, ra + i * 32, 0, lane);
 #pragma unroll
-    for (int j = 0; j < TN; ++j) fb[0][j] = frag<BN, BKM, KB>(lds + NS * IA, rb + j * 32, 0, lane);
+    for (int j = 0; j < TN; ++j) fb[0][j] = frag<BN, BKM>(lds + NS * IA, rb + j * 32, 0, lane);
     for (int t = 0; t < nk; ++t) {
       const int cur = t % NS;
       // the next tile into the buffer every wave finished reading before the last barrier
-      if (t + NS - 1 < nk) {
-        issue(t + NS - 1, (t + NS - 1) % NS);
-        issued = t + NS - 1;
-      }
+      if (t + NS - 1 < nk) issue(t + NS - 1, (t + NS - 1) % NS);
       const uint16_t* As = lds + cur * IA;
       const uint16_t* Bs = lds + NS * IA + cur * IB;
       if (do_rs) {
-        if constexpr (AK) img_rowsum8<BM, NT, KB>(As, tid, rs8);
-        else rs += img_rowsum<BM, AK, NT, KB>(As, tid);
+        if constexpr (AK) img_rowsum8<BM, NT>(As, tid, rs8);
+        else rs += img_rowsum<BM, AK, NT>(As, tid);
       }
 #pragma unroll
       for (int s = 0; s < SS; ++s) {
         const int u = s & 1;
         if (s < SS - 1) {
 #pragma unroll
-          for (int i = 0; i < TM; ++i) fa[u ^ 1][i] = frag<BM, AK, KB>(As, ra + i * 32, s + 1, lane);
+          for (int i = 0; i < TM; ++i) fa[u ^ 1][i] = frag<BM, AK>(As, ra + i * 32, s + 1, lane);
 #pragma unroll
-          for (int j = 0; j < TN; ++j) fb[u ^ 1][j] = frag<BN, BKM, KB>(Bs, rb + j * 32, s + 1, lane);
+          for (int j = 0; j < TN; ++j) fb[u ^ 1][j] = frag<BN, BKM>(Bs, rb + j * 32, s + 1, lane);
         }
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -436,20 +402,25 @@ __device__ __forceinline__ void bf16_tile(
             acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[u][i], fb[u][j], acc[i][j], 0, 0, 0);
         if (s == SS - 2) {
           // tile t+1 landed and every wave is past its reads of tile t-1
-          if (t + 1 < nk) sync_tile(t + 1, issued);
-          else if constexpr (NS == 2) __syncthreads();
+          // One barrier per branch, on purpose: with a single call (and likewise with the
+          // prologue's loop above written as a plain issue(0, 0)) hipcc lays the K loop out
+          // differently, e.g. 12.3 instead of 10.7 KB of code for the 128 x 128 tile. Folding
+          // either moves every gemm_bf16_kernel and group kernel (scripts/kernel_digest.py on
+          // gemm_bf16.o before and after shows it): do it only with a re-measurement of the
+          // cfg5 step (scripts/gemm_bf16_bench.py), not as a tidy-up.
+          if (t + 1 < nk) __syncthreads();
+          else __syncthreads();
           if (t + 1 < nk) {
             const int nx = (t + 1) % NS;
 #pragma unroll
-            for (int i = 0; i < TM; ++i) fa[0][i] = frag<BM, AK, KB>(lds + nx * IA, ra + i * 32, 0, lane);
+            for (int i = 0; i < TM; ++i) fa[0][i] = frag<BM, AK>(lds + nx * IA, ra + i * 32, 0, lane);
 #pragma unroll
             for (int j = 0; j < TN; ++j)
-              fb[0][j] = frag<BN, BKM, KB>(lds + NS * IA + nx * IB, rb + j * 32, 0, lane);
+              fb[0][j] = frag<BN, BKM>(lds + NS * IA + nx * IB, rb + j * 32, 0, lane);
           }
         }
       }
     }
-    if constexpr (NS > 2) wait_vmcnt<0>();
     __syncthreads();  // the epilogue reuses the staging array
   }
   if constexpr (AK) {
@@ -474,57 +445,35 @@ __device__ __forceinline__ void bf16_tile(
                                                 ws_rowsum, kz);
 }
 
-template <int BM, int BN, int WM, int WN, int KB, int NS, bool TA, bool TB, int EPI, bool OBF>
+template <int BM, int BN, int WM, int WN, bool TA, bool TB, int EPI, bool OBF>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_kernel(
     int M, int N, int K, int k_per_split, int tiles_n, int tiles, float alpha,
     const uint16_t* __restrict__ A, int64_t lda, const uint16_t* __restrict__ B, int64_t ldb,
     float beta, void* __restrict__ C, int64_t ldc, const float* __restrict__ bias, float slope,
     const uint16_t* __restrict__ dact, int64_t lddact, float* __restrict__ rowsum,
     float* __restrict__ ws, float* __restrict__ ws_rowsum) {
-  __shared__ __attribute__((aligned(16))) uint16_t lds[bf16_lds_u16<BM, BN, WM, WN, KB, NS>()];
-  // XCD-aware tile order (as gemm.hip): blocks b, b + 8, ... share an XCD and get a
-  // contiguous run of row-major tile ids, so the tiles sharing A rows meet in one L2
-  const int b = blockIdx.x;
-  const int q8 = tiles / 8, r8 = tiles % 8, x8 = b % 8;
-  const int tile = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + b / 8;
-  bf16_tile<BM, BN, WM, WN, KB, NS, TA, TB, EPI, OBF>(lds, M, N, K, k_per_split, blockIdx.z, tile / tiles_n,
-                                                      tile % tiles_n, alpha, A, lda, B, ldb, beta, C, ldc, bias,
-                                                      slope, dact, lddact, rowsum, ws, ws_rowsum);
+  __shared__ __attribute__((aligned(16))) uint16_t lds[bf16_lds_u16<BM, BN, WM, WN>()];
+  // XCD-aware tile order (as gemm.hip): the tiles sharing A rows meet in one L2
+  const int tile = xcd_item(tiles);
+  bf16_tile<BM, BN, WM, WN, TA, TB, EPI, OBF>(lds, M, N, K, k_per_split, blockIdx.z, tile / tiles_n, tile % tiles_n,
+                                              alpha, A, lda, B, ldb, beta, C, ldc, bias, slope, dact, lddact, rowsum,
+                                              ws, ws_rowsum);
 }
 
 // Grouped split-K partials (pg_gemm_bf16_group): every part's items (tiles x K slices,
 // slice-major) end to end in one launch, XCD-aware over the items as gemm_x3's group.
-struct BPart {
-  int M, N, K, kps, tiles_n, tiles, first_item;
-  const uint16_t* A;
-  int64_t lda;
-  const uint16_t* B;
-  int64_t ldb;
-  float* ws;
-  float* ws_rowsum;
-  float* rowsum;
-};
-constexpr int kBMaxParts = 16;
-struct BGroup {
-  BPart p[kBMaxParts];
-  int n, items;
-};
+using BGroup = GemmGroup<uint16_t>;
 
 template <int BM, int BN, int WM, int WN, bool TA, bool TB>
 __global__ __launch_bounds__(64 * WM * WN) void gemm_bf16_group_kernel(BGroup g) {
-  __shared__ __attribute__((aligned(16))) uint16_t lds[bf16_lds_u16<BM, BN, WM, WN, BK, 2>()];
-  const int b = blockIdx.x;
-  const int q8 = g.items / 8, r8 = g.items % 8, x8 = b % 8;
-  const int item = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + b / 8;
-  int k = 0;
-  while (k + 1 < g.n && item >= g.p[k + 1].first_item) ++k;
-  const BPart& p = g.p[k];
+  __shared__ __attribute__((aligned(16))) uint16_t lds[bf16_lds_u16<BM, BN, WM, WN>()];
+  const int item = xcd_item(g.items);
+  const GemmPart<uint16_t>& p = group_part(g, item);
   const int local = item - p.first_item;
   const int kz = local / p.tiles, tile = local % p.tiles;
-  bf16_tile<BM, BN, WM, WN, BK, 2, TA, TB, EPI_SPLIT, false>(lds, p.M, p.N, p.K, p.kps, kz, tile / p.tiles_n,
-                                                             tile % p.tiles_n, 1.f, p.A, p.lda, p.B, p.ldb, 0.f,
-                                                             nullptr, 0, nullptr, 0.f, nullptr, 0, p.rowsum, p.ws,
-                                                             p.ws_rowsum);
+  bf16_tile<BM, BN, WM, WN, TA, TB, EPI_SPLIT, false>(lds, p.M, p.N, p.K, p.kps, kz, tile / p.tiles_n, tile % p.tiles_n,
+                                                      1.f, p.A, p.lda, p.B, p.ldb, 0.f, nullptr, 0, nullptr, 0.f,
+                                                      nullptr, 0, p.rowsum, p.ws, p.ws_rowsum);
 }
 
 // ---- 256 x 256 ping-pong kernel for A[m][k] x B[n][k]^T (both operands row images) -----
@@ -565,9 +514,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(
   static_assert(64 * EPS * 4 <= 2 * BUF * 2, "epilogue band fits");
   __shared__ __attribute__((aligned(16))) uint16_t lds[2 * BUF];
 
-  const int b = blockIdx.x;
-  const int q8 = tiles / 8, r8 = tiles % 8, x8 = b % 8;
-  const int tile = (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + b / 8;
+  const int tile = xcd_item(tiles);
   const int m0 = (tile / tiles_n) * 256, n0 = (tile % tiles_n) * 256;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -610,7 +557,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
         fa[i][ks] = *reinterpret_cast<const bf16x8*>(
-            S + img_off<256, false, 64>(wr * 128 + asub * 64 + i * 16 + l16, 32 * ks + kq));
+            S + img_off<256, false>(wr * 128 + asub * 64 + i * 16 + l16, 32 * ks + kq));
   };
   auto read_b = [&](const uint16_t* S, int bsub) {
 #pragma unroll
@@ -618,7 +565,7 @@ __global__ __launch_bounds__(512) void gemm_bf16_pp_kernel(
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks)
         fb[j][ks] = *reinterpret_cast<const bf16x8*>(
-            S + IMG + img_off<256, false, 64>(wc * 64 + bsub * 32 + j * 16 + l16, 32 * ks + kq));
+            S + IMG + img_off<256, false>(wc * 64 + bsub * 32 + j * 16 + l16, 32 * ks + kq));
   };
   auto mfma = [&](int asub, int bsub) {
     __builtin_amdgcn_s_setprio(1);
@@ -749,76 +696,9 @@ struct Args {
   float* ws_rowsum;
 };
 
-template <int BM, int BN, int WM, int WN, bool TA, bool TB, bool OBF>
-int launch_epi(int epi, dim3 grid, hipStream_t st, const Args& a) {
-  // KB = 64 x 2 stages. PG_BF16_DEEP=1 (build-time experiment): 256 x 256 tiles with KB = 32
-  // x 4 stages and counted vmcnt instead; measured slower (fwd.cat 670 us either way, 8192^3
-  // 1580 vs 1180 us): the DMA latency is not what holds this structure back.
-  constexpr bool deep = PG_BF16_DEEP && BM == 256 && BN == 256;
-  constexpr bool t2 = PG_BF16_T2 && BM == 256 && BN == 128;
-  constexpr int KB = deep || t2 ? 32 : 64;
-  constexpr int NS = deep ? 4 : t2 ? PG_BF16_T2_NS : 2;
-#define PG_L(EPI_)                                                                                    \
-  hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, WM, WN, KB, NS, TA, TB, EPI_, OBF>), grid, dim3(64 * WM * WN), 0, st, \
-                     a.M, a.N, a.K, a.kps, a.tiles_n, a.tiles, a.alpha, a.A, a.lda, a.B, a.ldb,   \
-                     a.beta, a.C, a.ldc, a.bias, a.slope, a.dact, a.lddact, a.rowsum, a.ws,      \
-                     a.ws_rowsum)
-  switch (epi) {
-    case EPI_NONE: PG_L(EPI_NONE); break;
-    case EPI_RELU: PG_L(EPI_RELU); break;
-    case EPI_LEAKY: PG_L(EPI_LEAKY); break;
-    case EPI_DRELU: PG_L(EPI_DRELU); break;
-    case EPI_DLEAKY: PG_L(EPI_DLEAKY); break;
-    case EPI_SPLIT:
-      if constexpr (!OBF) {
-        PG_L(EPI_SPLIT);
-        break;
-      }
-      return PG_ERR_INVALID;
-    default: return PG_ERR_INVALID;
-  }
-#undef PG_L
-  return PG_OK;
-}
-
-template <int BM, int BN, int WM, int WN>
-int launch_tile(bool ta, bool tb, bool obf, int epi, dim3 grid, hipStream_t st, const Args& a) {
-#define PG_T(TA_, TB_)                                                      \
-  return obf ? launch_epi<BM, BN, WM, WN, TA_, TB_, true>(epi, grid, st, a) \
-             : launch_epi<BM, BN, WM, WN, TA_, TB_, false>(epi, grid, st, a)
-  if (!ta && !tb) PG_T(false, false);
-  if (!ta && tb) PG_T(false, true);
-  if (ta && !tb) PG_T(true, false);
-  PG_T(true, true);
-#undef PG_T
-}
-
-#ifndef PG_BF16_PP
-#define PG_BF16_PP 1  // 0 (variant builds): the two-phase 256 x 256 kernel for A B^T as well
-#endif
-int launch_pp(bool obf, int epi, hipStream_t st, const Args& a) {
-#define PG_P(EPI_, OBF_)                                                                                    \
-  hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI_, OBF_>), dim3((unsigned)a.tiles), dim3(512), 0, st, a.M, a.N, a.K, \
-                     a.tiles_n, a.tiles, a.alpha, a.A, a.lda, a.B, a.ldb, a.beta, a.C, a.ldc, a.bias, a.slope,  \
-                     a.dact, a.lddact)
-#define PG_PO(EPI_) \
-  if (obf) PG_P(EPI_, true); else PG_P(EPI_, false)
-  switch (epi) {
-    case EPI_NONE: PG_PO(EPI_NONE); break;
-    case EPI_RELU: PG_PO(EPI_RELU); break;
-    case EPI_LEAKY: PG_PO(EPI_LEAKY); break;
-    case EPI_DRELU: PG_PO(EPI_DRELU); break;
-    case EPI_DLEAKY: PG_PO(EPI_DLEAKY); break;
-    default: return PG_ERR_INVALID;
-  }
-#undef PG_PO
-#undef PG_P
-  return PG_OK;
-}
-
 // Tile choice. The bf16 MFMA rate (4096 flop/clk/CU) needs ~64 flop per byte staged
-// from L2 (BM BN / (BM + BN) per workgroup): 256 x 256 tiles (4 waves of 128 x 128, the
-// 256 accumulators in AGPRs at one wave per SIMD; one 128-KiB workgroup per CU) wherever they still give >= 1 workgroup per CU, 128 x 128
+// from L2 (BM BN / (BM + BN) per workgroup): 256 x 256 tiles (eight waves of 128 x 64; one
+// 128-KiB workgroup per CU) wherever they still give >= 1 workgroup per CU, 128 x 128
 // (two per CU) next, 128 x 64 / 64 x 64 for narrow or small products. Split products
 // (weight gradients) use 256 x 256 when both sides allow it, else 64 x 64.
 #ifndef PG_BF16_TILE_FORCE
@@ -836,27 +716,66 @@ inline void pick_tile(int64_t M, int64_t N, int64_t K, int split, int& bm, int& 
     if (M >= 256 && N >= 256) bm = bn = 256;
     return;
   }
-#ifndef PG_BF16_SMALLK_TILE
-#define PG_BF16_SMALLK_TILE 0  // variant builds: BM * 1000 + BN for products with K <= 128
-#endif
-  if constexpr (PG_BF16_SMALLK_TILE != 0) {
-    if (K <= 128) {
-      bm = PG_BF16_SMALLK_TILE / 1000;
-      bn = PG_BF16_SMALLK_TILE % 1000;
-      return;
-    }
-  }
   // (a short K leaves a 256 x 256 workgroup, alone on its CU, mostly in its epilogue)
-  if (PG_BF16_T2 && N >= 128 && K >= 384 && tiles(256, 128) >= 512) {
-    bm = 256;
-    bn = 128;
-  } else if (N >= 256 && K >= 384 && tiles(256, 256) >= 256) {
+  if (N >= 256 && K >= 384 && tiles(256, 256) >= 256) {
     bm = bn = 256;
   } else if (N > 64 && tiles(128, 128) >= 512) {
     bm = bn = 128;
   } else if (tiles(128, 64) >= 512) {
     bm = 128;
   }
+}
+// the tiles pick_tile can return: split products 256 x 256 or 64 x 64, the others also
+// 128 x 128 and 128 x 64 (256 x 128 and 64 x 128 only when forced)
+template <int BM, int BN>
+constexpr bool tile_built(bool split) {
+  if (PG_BF16_TILE_FORCE != 0) return BM * 1000 + BN == PG_BF16_TILE_FORCE;
+  if (BM == BN && (BM == 256 || BM == 64)) return true;
+  return !split && BM == 128 && (BN == 128 || BN == 64);
+}
+
+// the two-phase kernel on the picked tile
+int launch(int bm, int bn, bool ta, bool tb, bool obf, int epi, int n_split, hipStream_t st, const Args& a) {
+  return dispatch_tile<Tile<256, 256>, Tile<256, 128>, Tile<128, 128>, Tile<128, 64>, Tile<64, 128>, Tile<64, 64>>(
+      bm, bn, [&](auto tile) {
+        return dispatch_flags(ta, tb, [&](auto ta_, auto tb_) {
+          return dispatch_flag(obf, [&](auto obf_) {
+            return dispatch_epi(epi, [&](auto epi_) {
+              constexpr int BM = decltype(tile)::bm, BN = decltype(tile)::bn, EPI = decltype(epi_)::value;
+              constexpr bool big = BM == 256 && BN == 256, OBF = decltype(obf_)::value;
+              constexpr int WM = big ? kBigWM : 2, WN = big ? kBigWN : 2;
+              // (split-K partials are f32)
+              if constexpr (!tile_built<BM, BN>(EPI == EPI_SPLIT) || (EPI == EPI_SPLIT && OBF)) {
+                return (int)PG_ERR_INVALID;
+              } else {
+                hipLaunchKernelGGL(
+                    (gemm_bf16_kernel<BM, BN, WM, WN, decltype(ta_)::value, decltype(tb_)::value, EPI, OBF>),
+                    dim3(a.tiles, 1, n_split), dim3(64 * WM * WN), 0, st, a.M, a.N, a.K, a.kps, a.tiles_n, a.tiles,
+                    a.alpha, a.A, a.lda, a.B, a.ldb, a.beta, a.C, a.ldc, a.bias, a.slope, a.dact, a.lddact, a.rowsum,
+                    a.ws, a.ws_rowsum);
+                return (int)PG_OK;
+              }
+            });
+          });
+        });
+      });
+}
+
+// the ping-pong kernel (256 x 256 tiles of A B^T, no split-K, no row sums)
+int launch_pp(bool obf, int epi, hipStream_t st, const Args& a) {
+  return dispatch_flag(obf, [&](auto obf_) {
+    return dispatch_epi(epi, [&](auto epi_) {
+      constexpr int EPI = decltype(epi_)::value;
+      if constexpr (EPI == EPI_SPLIT) {
+        return (int)PG_ERR_INVALID;
+      } else {
+        hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI, decltype(obf_)::value>), dim3((unsigned)a.tiles), dim3(512), 0, st,
+                           a.M, a.N, a.K, a.tiles_n, a.tiles, a.alpha, a.A, a.lda, a.B, a.ldb, a.beta, a.C, a.ldc,
+                           a.bias, a.slope, a.dact, a.lddact);
+        return (int)PG_OK;
+      }
+    });
+  });
 }
 
 }  // namespace
@@ -887,53 +806,34 @@ int pg_gemm_bf16(int transa, int transb, int64_t M, int64_t N, int64_t K, float 
                  const void* A, int64_t lda, const void* B, int64_t ldb, float beta, void* C,
                  int64_t ldc, int c_dtype, const pg_gemm_epilogue_t* ep, int split_k, void* ws,
                  size_t ws_bytes, pg_stream_t stream) {
-  const pg_gemm_epilogue_t none{nullptr, PG_ACT_NONE, 0.f, nullptr, 0, nullptr};
-  if (!ep) ep = &none;
-  const int act = ep->act;
-  if (M < 0 || N < 0 || K < 0 || M > INT32_MAX || N > INT32_MAX || K > INT32_MAX)
-    return pg::set_error(PG_ERR_INVALID, "pg_gemm_bf16: bad sizes");
-  if (c_dtype != PG_DTYPE_F32 && c_dtype != PG_DTYPE_BF16)
-    return pg::set_error(PG_ERR_INVALID, "pg_gemm_bf16: c_dtype must be PG_DTYPE_F32 or PG_DTYPE_BF16");
-  if (ldc < N || (!transa && lda < K) || (transa && lda < M) || (!transb && ldb < N) ||
-      (transb && ldb < K))
-    return pg::set_error(PG_ERR_INVALID, "pg_gemm_bf16: leading dimension too small");
-  if (act != PG_ACT_NONE && act != PG_ACT_RELU && act != PG_ACT_LEAKY)
-    return pg::set_error(PG_ERR_INVALID, "pg_gemm_bf16: bad act %d", act);
-  if (split_k < 1) split_k = 1;
+  if (!ep) ep = &kNoEpilogue;
   const bool obf = c_dtype == PG_DTYPE_BF16;
-  if (split_k > 1 && (obf || ep->bias || act != PG_ACT_NONE || ep->dact || (beta != 0.f && beta != 1.f)))
-    return pg::set_error(PG_ERR_INVALID,
-                         "pg_gemm_bf16: split_k > 1 needs an f32 C, no bias/act, beta 0|1");
-  if (ep->dact && (act == PG_ACT_NONE || ep->lddact < N))
-    return pg::set_error(PG_ERR_INVALID, "pg_gemm_bf16: dact needs act relu|leaky and lddact >= N");
+  if (split_k < 1) split_k = 1;
+  if (const int rc = check_product("pg_gemm_bf16", transa, transb, M, N, K, lda, ldb, ldc, *ep, beta, split_k, obf,
+                                   "needs an f32 C, no bias/act, beta 0|1",
+                                   c_dtype != PG_DTYPE_F32 && c_dtype != PG_DTYPE_BF16
+                                       ? "c_dtype must be PG_DTYPE_F32 or PG_DTYPE_BF16"
+                                       : nullptr))
+    return rc;
   if (M == 0 || N == 0) return pg::ok();
   // operand layout requirements of the DMA staging (16-B units of 8 bf16)
   const int64_t ext_a = transa ? M : K, ext_b = transb ? K : N;
-  if (!al16(A) || !al16(B) || !al16(C) || lda % 8 || ldb % 8 || ext_a % 8 || ext_b % 8 || N % 4 ||
-      ldc % (obf ? 4 : 4) || (ep->bias && !al16(ep->bias)) ||
-      (ep->dact && (((uintptr_t)ep->dact & 7) || ep->lddact % 4)))
+  if (!al16(A) || !al16(B) || !al16(C) || lda % 8 || ldb % 8 || ext_a % 8 || ext_b % 8 || N % 4 || ldc % 4 ||
+      (ep->bias && !al16(ep->bias)) || (ep->dact && (((uintptr_t)ep->dact & 7) || ep->lddact % 4)))
     return pg::set_error(PG_ERR_UNSUPPORTED,
                          "pg_gemm_bf16: operands must be 16-B aligned with leading dimensions and "
                          "contiguous extents multiples of 8, N and ldc multiples of 4");
   if (split_k > 1 && ws_bytes < pg_gemm_bf16_workspace(M, N, K, split_k))
     return pg::set_error(PG_ERR_WORKSPACE, "pg_gemm_bf16: workspace too small");
   if (split_k > 1 && !al16(ws)) return pg::set_error(PG_ERR_INVALID, "pg_gemm_bf16: workspace alignment");
-  int kps = (int)K;
-  if (split_k > 1) {
-    kps = (int)((K + split_k - 1) / split_k);
-    kps = (kps + BK - 1) / BK * BK;
-    split_k = (int)((K + kps - 1) / kps);
-    if (split_k < 1) split_k = 1;
-  }
+  const int kps = k_slices(K, BK, split_k);
   const bool split = split_k > 1;
-  int bm, bn;
+  int bm, bn, tiles_n, tiles;
   pick_tile(M, N, K, split_k, bm, bn);
   // a k image needs >= 8 valid rows for its clamped 16-B chunks
   if ((transa && M < 8) || (!transb && N < 8))
     return pg::set_error(PG_ERR_UNSUPPORTED, "pg_gemm_bf16: row-contiguous operand narrower than 8");
-  const int tiles_n = (int)((N + bn - 1) / bn);
-  const int tiles = tiles_n * (int)((M + bm - 1) / bm);
-  dim3 grid((unsigned)tiles, 1, (unsigned)split_k);
+  tile_grid(M, N, bm, bn, tiles_n, tiles);
   hipStream_t st = (hipStream_t)stream;
   float* wsf = split ? (float*)ws : nullptr;
   const Args a{(int)M, (int)N, (int)K, kps, tiles_n, tiles, alpha, (const uint16_t*)A, lda,
@@ -941,32 +841,12 @@ int pg_gemm_bf16(int transa, int transb, int64_t M, int64_t N, int64_t K, float 
                (const uint16_t*)ep->dact, ep->lddact, ep->rowsum, wsf,
                split ? wsf + (int64_t)split_k * M * N : nullptr};
   const bool ta = transa != 0, tb = transb != 0;
-  const int epi = split ? EPI_SPLIT
-                        : ep->dact ? (act == PG_ACT_RELU ? EPI_DRELU : EPI_DLEAKY)
-                                   : (act == PG_ACT_RELU ? EPI_RELU : act == PG_ACT_LEAKY ? EPI_LEAKY : EPI_NONE);
-  int rc;
-  if (PG_BF16_PP && bm == 256 && bn == 256 && !ta && tb && !split && !ep->rowsum) rc = launch_pp(obf, epi, st, a);
-  else if (bm == 256 && bn == 256) rc = launch_tile<256, 256, PG_BF16_WM, PG_BF16_WN>(ta, tb, obf, epi, grid, st, a);
-  else if (bm == 256) rc = launch_tile<256, 128, 2, 2>(ta, tb, obf, epi, grid, st, a);
-  else if (bm == 128 && bn == 128) rc = launch_tile<128, 128, 2, 2>(ta, tb, obf, epi, grid, st, a);
-  else if (bm == 128) rc = launch_tile<128, 64, 2, 2>(ta, tb, obf, epi, grid, st, a);
-  else if (bn == 128) rc = launch_tile<64, 128, 2, 2>(ta, tb, obf, epi, grid, st, a);
-  else rc = launch_tile<64, 64, 2, 2>(ta, tb, obf, epi, grid, st, a);
+  const int epi = epi_code(*ep, split);
+  const int rc = bm == 256 && bn == 256 && !ta && tb && !split && !ep->rowsum
+                     ? launch_pp(obf, epi, st, a)
+                     : launch(bm, bn, ta, tb, obf, epi, split_k, st, a);
   if (rc != PG_OK) return pg::set_error(rc, "pg_gemm_bf16: dispatch failed");
-  if (split) {
-    const int64_t n = (N % 4 == 0 ? M * N / 4 : M * N) + (ep->rowsum ? M : 0);  // work units
-    const int G = splitk_groups(split_k);
-    const int opb = 256 / G;
-    const int blocks = (int)std::min<int64_t>(8192, (n + opb - 1) / opb);
-#define PG_R(G_)                                                                              \
-  hipLaunchKernelGGL(splitk_reduce_kernel<G_>, dim3(blocks), dim3(256), 0, st, (const float*)wsf, \
-                     split_k, (int)M, (int)N, alpha, beta, (float*)C, ldc, (const float*)a.ws_rowsum, \
-                     ep->rowsum)
-    if (G == 1) PG_R(1);
-    else if (G == 4) PG_R(4);
-    else PG_R(16);
-#undef PG_R
-  }
+  if (split) launch_combine(wsf, split_k, M, N, alpha, beta, (float*)C, ldc, a.ws_rowsum, ep->rowsum, st);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess)
     return pg::set_error((int)e, "pg_gemm_bf16: launch failed: %s", hipGetErrorString(e));
@@ -981,19 +861,12 @@ namespace {
 // when its tiles waste at most 4x its area; one K-slice count for the members, the one
 // (<= 64, slices >= 3 BK) whose items fill whole rounds of 256 workgroups best (the
 // smallest such count within 1 %).
-struct BPlan {
-  bool in[kBMaxParts];
-  int split[kBMaxParts];
-  int kps[kBMaxParts];
-  size_t off[kBMaxParts + 1];
-};
-
 inline bool bgroup_member(const pg_gemm_part_t& q) {
   const int64_t pm = (q.M + 255) / 256 * 256, pn = (q.N + 255) / 256 * 256;
   return q.M > 0 && q.N > 0 && pm * pn <= 4 * q.M * q.N;
 }
 
-inline void bgroup_plan(const pg_gemm_part_t* parts, int n, BPlan& g) {
+inline void bgroup_plan(const pg_gemm_part_t* parts, int n, GroupPlan& g) {
   int64_t T = 0, kmin = INT64_MAX;
   for (int p = 0; p < n; ++p) {
     g.in[p] = bgroup_member(parts[p]);
@@ -1011,22 +884,9 @@ inline void bgroup_plan(const pg_gemm_part_t* parts, int n, BPlan& g) {
       if (fill > bf + 0.01) bf = fill, best = sc;
     }
   }
-  size_t off = 0;
-  for (int p = 0; p < n; ++p) {
-    const pg_gemm_part_t& q = parts[p];
-    g.split[p] = 1;
-    g.kps[p] = BK;
-    g.off[p] = off;
-    if (!g.in[p]) continue;
-    int64_t sp = std::max<int64_t>(1, std::min<int64_t>(best, q.K / (3 * BK)));
-    int64_t kps = (q.K + sp - 1) / sp;
-    kps = std::max<int64_t>(BK, (kps + BK - 1) / BK * BK);
-    sp = std::max<int64_t>(1, (q.K + kps - 1) / kps);
-    g.split[p] = (int)sp;
-    g.kps[p] = (int)kps;
-    off += ((size_t)sp * (size_t)q.M * (size_t)(q.N + 1) * 4 + 255) / 256 * 256;
-  }
-  g.off[n] = off;
+  for (int p = 0; p < n; ++p)
+    g.split[p] = (int)std::max<int64_t>(1, std::min<int64_t>(best, parts[p].K / (3 * BK)));
+  group_layout(parts, n, BK, g);
 }
 
 inline bool bpart_layout_ok(const pg_gemm_part_t& q) {
@@ -1046,8 +906,8 @@ int bpart_alone(const pg_gemm_part_t& q, void* ws, size_t ws_bytes, pg_stream_t 
 extern "C" {
 
 size_t pg_gemm_bf16_group_workspace(const pg_gemm_part_t* parts, int n) {
-  if (n <= 0 || n > kBMaxParts || !parts) return 0;
-  BPlan g;
+  if (n <= 0 || n > kMaxParts || !parts) return 0;
+  GroupPlan g;
   bgroup_plan(parts, n, g);
   size_t need = g.off[n];
   for (int p = 0; p < n; ++p) {
@@ -1058,20 +918,14 @@ size_t pg_gemm_bf16_group_workspace(const pg_gemm_part_t* parts, int n) {
 }
 
 int pg_gemm_bf16_group(const pg_gemm_part_t* parts, int n, void* ws, size_t ws_bytes, pg_stream_t stream) {
-  if (n < 0 || n > kBMaxParts || (n > 0 && !parts))
-    return pg::set_error(PG_ERR_INVALID, "pg_gemm_bf16_group: 0..%d parts", kBMaxParts);
+  if (n < 0 || n > kMaxParts || (n > 0 && !parts))
+    return pg::set_error(PG_ERR_INVALID, "pg_gemm_bf16_group: 0..%d parts", kMaxParts);
   if (n == 0) return pg::ok();
-  for (int p = 0; p < n; ++p) {
-    const pg_gemm_part_t& q = parts[p];
-    if (q.M < 0 || q.N < 0 || q.K < 0 || q.M > INT32_MAX || q.N > INT32_MAX || q.K > INT32_MAX || q.ldc < q.N ||
-        (q.transa ? q.lda < q.M : q.lda < q.K) || (q.transb ? q.ldb < q.K : q.ldb < q.N) ||
-        (q.beta != 0.f && q.beta != 1.f) || (q.M > 0 && q.N > 0 && !q.C) ||
-        (q.M > 0 && q.N > 0 && q.K > 0 && (!q.A || !q.B)))
-      return pg::set_error(PG_ERR_INVALID, "pg_gemm_bf16_group: bad part %d", p);
-  }
+  for (int p = 0; p < n; ++p)
+    if (!part_ok(parts[p])) return pg::set_error(PG_ERR_INVALID, "pg_gemm_bf16_group: bad part %d", p);
   if (ws_bytes < pg_gemm_bf16_group_workspace(parts, n) || !ws || !al16(ws))
     return pg::set_error(PG_ERR_WORKSPACE, "pg_gemm_bf16_group: workspace too small or misaligned");
-  BPlan g;
+  GroupPlan g;
   bgroup_plan(parts, n, g);
   int first = -1;
   bool grouped = true;
@@ -1089,39 +943,13 @@ int pg_gemm_bf16_group(const pg_gemm_part_t* parts, int n, void* ws, size_t ws_b
     return pg::ok();
   }
   BGroup bg{};
-  pg_splitk_job_t jobs[kBMaxParts];
-  int items = 0, nj = 0;
-  for (int p = 0; p < n; ++p) {
-    if (!g.in[p]) continue;
-    const pg_gemm_part_t& q = parts[p];
-    float* w = (float*)((char*)ws + g.off[p]);
-    BPart& x = bg.p[nj];
-    x.M = (int)q.M; x.N = (int)q.N; x.K = (int)q.K; x.kps = g.kps[p];
-    x.tiles_n = (int)((q.N + 255) / 256);
-    x.tiles = x.tiles_n * (int)((q.M + 255) / 256);
-    x.first_item = items;
-    x.A = (const uint16_t*)q.A; x.lda = q.lda; x.B = (const uint16_t*)q.B; x.ldb = q.ldb;
-    x.ws = w;
-    x.ws_rowsum = w + (int64_t)g.split[p] * q.M * q.N;
-    x.rowsum = q.rowsum;
-    items += x.tiles * g.split[p];
-    pg_splitk_job_t& j = jobs[nj];
-    j.ws = w; j.split_k = g.split[p]; j.M = q.M; j.N = q.N;
-    j.alpha = 1.f; j.beta = q.beta; j.C = q.C; j.ldc = q.ldc; j.rowsum = q.rowsum;
-    ++nj;
-  }
-  bg.n = nj;
-  bg.items = items;
-  const bool ta = parts[first].transa != 0, tb = parts[first].transb != 0;
-  const dim3 grid((unsigned)items), block(64 * PG_BF16_WM * PG_BF16_WN);
-  hipStream_t st = (hipStream_t)stream;
-#define PG_G(TA_, TB_) \
-  hipLaunchKernelGGL((gemm_bf16_group_kernel<256, 256, PG_BF16_WM, PG_BF16_WN, TA_, TB_>), grid, block, 0, st, bg)
-  if (ta && !tb) PG_G(true, false);
-  else if (!ta && !tb) PG_G(false, false);
-  else if (!ta && tb) PG_G(false, true);
-  else PG_G(true, true);
-#undef PG_G
+  pg_splitk_job_t jobs[kMaxParts];
+  const int nj = group_fill(parts, n, g, 256, 256, ws, bg, jobs);
+  dispatch_flags(parts[first].transa != 0, parts[first].transb != 0, [&](auto ta, auto tb) {
+    hipLaunchKernelGGL((gemm_bf16_group_kernel<256, 256, kBigWM, kBigWN, decltype(ta)::value, decltype(tb)::value>),
+                       dim3((unsigned)bg.items), dim3(64 * kBigWM * kBigWN), 0, (hipStream_t)stream, bg);
+    return (int)PG_OK;
+  });
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess)
     return pg::set_error((int)e, "pg_gemm_bf16_group: launch failed: %s", hipGetErrorString(e));

@@ -1,5 +1,7 @@
-// Pieces shared by the fp32 (gemm.hip) and bf16 (gemm_bf16.hip) GEMMs: the fused
-// epilogue modes and the deterministic split-K combine.
+// Device-side pieces shared by the GEMM families (gemm.hip, gemm_x3.hip, gemm_bf16.hip): the
+// fused epilogue modes, the deterministic split-K combine, the XCD item order, the grouped
+// launches' argument structs, and the three-piece kernels' launchers. The shared host code
+// is gemm_host.hpp.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -158,29 +160,50 @@ int gemm_x3_cat_launch(const X3Args& a, const float* A2, int64_t lda2, const flo
 // of the tile grid reads A[rows[i]] and writes C[rows[i]] (ta = false, EPI_NONE, no split-K).
 int gemm_x3_rows_launch(const X3Args& a, const int32_t* rows, int m_full, hipStream_t st);
 
-// Grouped split-K partials (pg_gemm_f32_group): one tile shape and one (ta, tb) for the
-// group. 128 x 256 (two workgroups per CU, each wave 64 x 128: a third less staging per
-// MFMA than 128 x 128): cfg2 GEMM 0.796 -> 0.790 ms per step, cfg3 1.867 -> 1.857
-// (scripts/ab_lib.sh, round 5); 128 x 64 was slower in round 4.
-#ifndef PG_X3_GROUP_TILE
-#define PG_X3_GROUP_TILE 128256  // variant builds: BM * 1000 + BN
-#endif
-constexpr int kX3GroupBM = PG_X3_GROUP_TILE / 1000, kX3GroupBN = PG_X3_GROUP_TILE % 1000;
-struct X3Part {
+// Grouped split-K partials (pg_gemm_f32_group, pg_gemm_bf16_group): the parts' items (tiles
+// x K slices, slice-major within a part) laid end to end in one launch; T = the operands'
+// storage type (float, or uint16_t bf16 bits).
+template <typename T>
+struct GemmPart {
   int M, N, K, kps, tiles_n, tiles, first_item;
-  const float* A;
+  const T* A;
   int64_t lda;
-  const float* B;
+  const T* B;
   int64_t ldb;
   float* ws;         // [n_split][M][N] slabs
   float* ws_rowsum;  // [n_split][M] row-sum slices
   float* rowsum;     // non-null: row sums wanted (the slices are written; the combine writes here)
 };
-constexpr int kX3MaxParts = 16;
-struct X3Group {
-  X3Part p[kX3MaxParts];
+constexpr int kMaxParts = 16;
+template <typename T>
+struct GemmGroup {
+  GemmPart<T> p[kMaxParts];
   int n, items;
 };
+// the part that holds `item` (returned by reference: hipcc then emits the same code as for
+// the loop spelled out in the kernel; returning the index does not)
+template <typename T>
+__device__ __forceinline__ const GemmPart<T>& group_part(const GemmGroup<T>& g, int item) {
+  int k = 0;
+  while (k + 1 < g.n && item >= g.p[k + 1].first_item) ++k;
+  return g.p[k];
+}
+
+// XCD-aware order over the `items` of a 1-D grid: workgroup b runs on XCD b % 8, and the
+// workgroups of one XCD take one contiguous range of the items (the bijective remap of
+// cdna_hip_programming.md section 5), so neighbouring items (the column tiles of a row tile,
+// the tiles of a K slice) share that XCD's L2.
+__device__ __forceinline__ int xcd_item(int items) {
+  const int b = blockIdx.x;
+  const int q8 = items / 8, r8 = items % 8, x8 = b % 8;
+  return (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + b / 8;
+}
+
+// The three-piece group's tile, 128 x 256 (two workgroups per CU, each wave 64 x 128: a
+// third less staging per MFMA than 128 x 128): cfg2 GEMM 0.796 -> 0.790 ms per step, cfg3
+// 1.867 -> 1.857 (scripts/ab_lib.sh, round 5); 128 x 64 was slower in round 4.
+constexpr int kX3GroupBM = 128, kX3GroupBN = 256;
+using X3Group = GemmGroup<float>;
 int gemm_x3_group_launch(const X3Group& g, bool ta, bool tb, hipStream_t st);
 
 // Threads per output of the split-K combine: enough slice groups that each thread sums

@@ -25,10 +25,14 @@
 //     ds_read_b64_tr_b16.
 // Requirements (the caller checks): 16-B aligned operands, leading dimensions and the
 // contiguous extents (K of a row image, M / N of a k image) multiples of 4.
+// The entry points are in gemm.hip; this file holds the kernels and their launchers
+// (gemm_common.hpp declares them). A tile is built where x3_tile_built (gemm_host.hpp, beside
+// pick_tile_x3) says the rule can return it.
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
 #include "gemm_common.hpp"
+#include "gemm_host.hpp"
 #include "x3_split.hpp"
 
 namespace {
@@ -73,21 +77,18 @@ __device__ __forceinline__ bf16x8 frag(const uint16_t* __restrict__ S, int rc, i
 // = (k, 4 rows).
 __device__ __attribute__((aligned(16))) float g_zero4[4] = {0.f, 0.f, 0.f, 0.f};  // never written; read as a float4
 
-#ifndef PG_X3_BUFLOAD
-#define PG_X3_BUFLOAD 1  // K tiles by buffer loads with per-unit 32-bit offsets (0: 64-bit addresses)
-#endif
-
-// One operand's buffer descriptor (wave-uniform: built from readfirstlane'd inputs, so the
-// compiler keeps it in SGPRs) covering `bytes` from P; every byte offset of the operand is
-// below 2^32 (x3_ok checks the extent on the host).
+// K tiles come by buffer loads with per-unit 32-bit offsets. One operand's buffer descriptor
+// (wave-uniform: built from readfirstlane'd inputs, so the compiler keeps it in SGPRs)
+// covering `bytes` from P; every byte offset of the operand is below 2^32 (x3_ok checks the
+// extent on the host).
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t x3_rsrc(const float* P, uint32_t bytes) { return pg_x3::rsrc(P, bytes); }
 constexpr uint32_t kX3Oob = 0xFFFFFFF0u;  // a byte offset past every descriptor's range: reads 0
 
-template <int ROWS, bool KMAJ, int NTH = NT>
+template <int ROWS, bool KMAJ>
 struct Stage {
   static constexpr int UNITS = ROWS * KS / 4;
-  static constexpr int PER = UNITS / NTH;
-  static_assert(PER >= 1 && UNITS % NTH == 0, "units per thread");
+  static constexpr int PER = UNITS / NT;
+  static_assert(PER >= 1 && UNITS % NT == 0, "units per thread");
   float4 v[PER];
 
   __device__ __forceinline__ static void unit_pos(int q, int& row, int& k) {
@@ -99,7 +100,6 @@ struct Stage {
       row = (q % (ROWS / 4)) << 2;
     }
   }
-#if PG_X3_BUFLOAD
   template <typename Addr>
   __device__ __forceinline__ void load(const Addr& a, __amdgpu_buffer_rsrc_t rs, uint32_t step_bytes, int kt, int kz1) {
 #pragma unroll
@@ -126,31 +126,13 @@ struct Stage {
       v[i] = __builtin_bit_cast(float4, make_uint4(x.x | y.x, x.y | y.y, x.z | y.z, x.w | y.w));
     }
   }
-#else
-  // rows past R read a clamped valid row (never stored); k past kz1 read as 0
-  __device__ __forceinline__ void load(const float* __restrict__ P, int64_t ld, int r0, int R, int k0,
-                                       int kz1, int tid) {
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      int row, k;
-      unit_pos(tid + i * NTH, row, k);
-      const int gk = k0 + k;
-      // straight-line: a unit past kz1 reads a 16-B zero word in global memory instead of
-      // being zeroed behind a branch, so every load is unconditional and the compiler
-      // counts the waits
-      const float* p = !KMAJ ? P + (int64_t)min(r0 + row, R - 1) * ld + gk
-                             : P + (int64_t)gk * ld + min(r0 + row, R - 4);
-      v[i] = *reinterpret_cast<const float4*>(gk < kz1 ? p : g_zero4);
-    }
-  }
-#endif
   // split and store the three pieces (images of IMG u16 each, consecutive)
   template <int IMG>
   __device__ __forceinline__ void store(uint16_t* __restrict__ S, int tid) const {
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
       int row, k;
-      unit_pos(tid + i * NTH, row, k);
+      unit_pos(tid + i * NT, row, k);
       uint2 pc[3];
       split4(v[i], pc);
       const int off = img_off<ROWS, KMAJ>(row, k);
@@ -173,26 +155,25 @@ struct Stage {
   }
 };
 
-#if PG_X3_BUFLOAD
 // A K tile's addressing, set up once per tile (shared by the register slots of a deeper
 // pipeline): the byte offset of each unit at the slice's first k (rows past R clamped to a
 // valid row, never stored) and its k within a K step. A step then costs one add, one
 // compare and one select per unit (a unit at or past kz1 reads through an out-of-range
 // offset: zeros), no 64-bit address arithmetic.
-template <int ROWS, bool KMAJ, int NTH = NT>
+template <int ROWS, bool KMAJ>
 struct StageAddr {
-  static constexpr int PER = Stage<ROWS, KMAJ, NTH>::PER;
+  static constexpr int PER = Stage<ROWS, KMAJ>::PER;
   // k image: unit i of a thread sits KQS k-rows below unit 0 in the same 4 rows, so one
   // offset and a wave-uniform stride describe them all; row image: every unit its own row
   // (clamped), one k
-  static constexpr int KQS = KMAJ ? NTH / (ROWS / 4) : 0;
+  static constexpr int KQS = KMAJ ? NT / (ROWS / 4) : 0;
   static constexpr int NOFF = KMAJ ? 1 : PER;
   uint32_t off_[NOFF];
   uint32_t ustride;  // KMAJ: bytes between consecutive units (wave-uniform)
   int kq0;
   __device__ __forceinline__ void setup(int64_t ld, int r0, int R, int k0, int tid) {
     int row, k;
-    Stage<ROWS, KMAJ, NTH>::unit_pos(tid, row, k);
+    Stage<ROWS, KMAJ>::unit_pos(tid, row, k);
     kq0 = k;
     if constexpr (KMAJ) {
       off_[0] = ((uint32_t)(k0 + k) * (uint32_t)ld + (uint32_t)min(r0 + row, R - 4)) * 4u;
@@ -200,7 +181,7 @@ struct StageAddr {
     } else {
 #pragma unroll
       for (int i = 0; i < PER; ++i) {
-        Stage<ROWS, KMAJ, NTH>::unit_pos(tid + i * NTH, row, k);
+        Stage<ROWS, KMAJ>::unit_pos(tid + i * NT, row, k);
         off_[i] = ((uint32_t)min(r0 + row, R - 1) * (uint32_t)ld + (uint32_t)(k0 + k)) * 4u;
       }
       ustride = 0;
@@ -211,17 +192,17 @@ struct StageAddr {
                                              int tid) {
     static_assert(!KMAJ, "a row list indexes a row image");
     int row, k;
-    Stage<ROWS, KMAJ, NTH>::unit_pos(tid, row, k);
+    Stage<ROWS, KMAJ>::unit_pos(tid, row, k);
     kq0 = k;
     int rid[PER];
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
-      Stage<ROWS, KMAJ, NTH>::unit_pos(tid + i * NTH, row, k);
+      Stage<ROWS, KMAJ>::unit_pos(tid + i * NT, row, k);
       rid[i] = rows[min(r0 + row, n - 1)];
     }
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
-      Stage<ROWS, KMAJ, NTH>::unit_pos(tid + i * NTH, row, k);
+      Stage<ROWS, KMAJ>::unit_pos(tid + i * NT, row, k);
       off_[i] = ((uint32_t)rid[i] * (uint32_t)ld + (uint32_t)(k0 + k)) * 4u;
     }
     ustride = 0;
@@ -232,29 +213,28 @@ struct StageAddr {
   }
   __device__ __forceinline__ int kq(int i) const { return kq0 + i * KQS; }
 };
-#endif
 
 // The accumulator tile leaves through LDS in PASSES row bands (16-B stores), with the
 // epilogue (alpha, beta C, bias, act / act', or the split-K partial slab).
 // RL (row-list form, EPI_NONE): M counts the listed rows, and tile row gr leaves to row
 // rows[gr] of C; the ids are loaded with the pass's other operands, ahead of the barrier.
-template <int BM, int BN, int EPI, int PASSES, int NTH = NT, bool RL = false>
-__device__ __forceinline__ void x3_store(const f32x16 (&acc)[BM / 64][BN / (32 * (NTH / 128))], float* __restrict__ img, int tid,
+template <int BM, int BN, int EPI, int PASSES, bool RL = false>
+__device__ __forceinline__ void x3_store(const f32x16 (&acc)[BM / 64][BN / (32 * (NT / 128))], float* __restrict__ img, int tid,
                                          int m0, int n0, int M, int N, int kz, float alpha, float beta,
                                          float* __restrict__ C, int64_t ldc, const float* __restrict__ bias,
                                          float slope, const float* __restrict__ dact, int64_t lddact,
                                          float* __restrict__ ws, const int32_t* __restrict__ rows = nullptr) {
   constexpr bool SPLIT = EPI == EPI_SPLIT;
   static_assert(!RL || EPI == EPI_NONE, "the row-list form has no epilogue");
-  constexpr int WN = NTH / 128;  // waves along N (2 x WN waves)
+  constexpr int WN = NT / 128;  // waves along N (2 x WN waves)
   constexpr int TM = BM / 64, TN = BN / (32 * WN);
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN, h = lane >> 5, l32 = lane & 31;
   constexpr int BAND = BM / PASSES;
-  constexpr int IT = BAND * BN / 4 / NTH;  // output quads per thread and pass
+  constexpr int IT = BAND * BN / 4 / NT;  // output quads per thread and pass
   constexpr int CH = IT < 8 ? IT : 8;     // quads whose operand loads are in flight together
   constexpr bool DACT = EPI == EPI_DRELU || EPI == EPI_DLEAKY;
-  static_assert(NTH % (BN / 4) == 0 && IT % CH == 0, "one column quad per thread");
+  static_assert(NT % (BN / 4) == 0 && IT % CH == 0, "one column quad per thread");
   // this thread's column quad is the same in every iteration: its bias is loaded once, and
   // the activation operand's quads are loaded CH at a time ahead of their use (clamped
   // addresses, no branch: behind the store loop's bounds test the loads would run one at a
@@ -269,14 +249,14 @@ __device__ __forceinline__ void x3_store(const f32x16 (&acc)[BM / 64][BN / (32 *
     if constexpr (RL) {
 #pragma unroll
       for (int q = 0; q < CH; ++q) {
-        const int row = ((c0 + q) * NTH + tid) / (BN / 4);
+        const int row = ((c0 + q) * NT + tid) / (BN / 4);
         rid[q] = rows[min(m0 + pass * BAND + row, M - 1)];
       }
     }
     if constexpr (DACT) {
 #pragma unroll
       for (int q = 0; q < CH; ++q) {
-        const int row = ((c0 + q) * NTH + tid) / (BN / 4);
+        const int row = ((c0 + q) * NT + tid) / (BN / 4);
         const int gr = min(m0 + pass * BAND + row, M - 1);
         y4[q] = *reinterpret_cast<const float4*>(dact + (int64_t)gr * lddact + gcl);
       }
@@ -302,7 +282,7 @@ __device__ __forceinline__ void x3_store(const f32x16 (&acc)[BM / 64][BN / (32 *
       if (c0 > 0) prefetch(pass, c0);
 #pragma unroll
       for (int q = 0; q < CH; ++q) {
-        const int u = (c0 + q) * NTH + tid;
+        const int u = (c0 + q) * NT + tid;
         const int row = u / (BN / 4), c = cq;
         const int gr = m0 + pass * BAND + row, gc = n0 + c;
         if (gr >= M || gc >= N) continue;
@@ -389,7 +369,7 @@ struct X3Cat {
 // RL: the row-list form (pg_gemm_f32_rows; TA = false, EPI_NONE, no split): M counts the
 // listed rows, `rows` names them, and A has m_full rows. Only the A tile's addressing (set
 // up once per tile) and the epilogue's C rows differ; the K loop is the same.
-template <int BM, int BN, bool TA, bool TB, int EPI, bool KCAT = false, int NTH = NT, bool RL = false>
+template <int BM, int BN, bool TA, bool TB, int EPI, bool KCAT = false, bool RL = false>
 __device__ __forceinline__ void x3_tile(
     uint16_t* __restrict__ lds, int M, int N, int K, int k_per_split, int kz, int tm, int tn, float alpha,
     const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb, float beta,
@@ -400,13 +380,13 @@ __device__ __forceinline__ void x3_tile(
   constexpr bool AK = TA, BKM = !TB;
   static_assert(!RL || (!TA && !KCAT && EPI == EPI_NONE), "row-list form: plain A, no epilogue");
   constexpr bool SPLIT = EPI == EPI_SPLIT;
-  constexpr int WN = NTH / 128;  // waves along N (2 x WN waves)
+  constexpr int WN = NT / 128;  // waves along N (2 x WN waves)
   constexpr int TM = BM / 64, TN = BN / (32 * WN);
   constexpr int IA = BM * KS, IB = BN * KS;  // one piece's image (u16)
   constexpr int BUF = 3 * (IA + IB);         // one buffer: [A_h A_m A_l | B_h B_m B_l]
   constexpr int STAGE_U16 = 2 * BUF;
   constexpr int PASSES = 2 * BM * BN > STAGE_U16 ? 2 : 1;  // f32 epilogue image in row bands
-  static_assert(x3_lds_u16<BM, BN>() * 2 >= NTH * 4 * 8, "row-sum scratch");
+  static_assert(x3_lds_u16<BM, BN>() * 2 >= NT * 4 * 8, "row-sum scratch");
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN, l32 = lane & 31;
@@ -423,10 +403,8 @@ __device__ __forceinline__ void x3_tile(
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  Stage<BM, AK, NTH> sa;
-  Stage<BN, BKM, NTH> sb;
-  static_assert(!KCAT || PG_X3_BUFLOAD, "K-concatenated operands need the buffer-load addressing");
-#if PG_X3_BUFLOAD
+  Stage<BM, AK> sa;
+  Stage<BN, BKM> sb;
   // operand extents in bytes (row image: R rows of ld; k image: K rows of ld); with KCAT the
   // first operands end at k = kcat (the host checked that extent, not K's)
   const int K1 = KCAT ? cat.kcat : K;
@@ -435,14 +413,14 @@ __device__ __forceinline__ void x3_tile(
   const uint32_t b_bytes = (uint32_t)(BKM ? ((int64_t)(K1 - 1) * ldb + N) * 4 : ((int64_t)(N - 1) * ldb + K1) * 4);
   const __amdgpu_buffer_rsrc_t rsa = x3_rsrc(A, a_bytes), rsb = x3_rsrc(B, b_bytes);
   const uint32_t a_kstride = AK ? (uint32_t)lda * 4u : 4u, b_kstride = BKM ? (uint32_t)ldb * 4u : 4u;
-  StageAddr<BM, AK, NTH> aa;
-  StageAddr<BN, BKM, NTH> ab;
+  StageAddr<BM, AK> aa;
+  StageAddr<BN, BKM> ab;
   if constexpr (RL) aa.setup_rows(lda, m0, rows, M, kz0, tid);
   else aa.setup(lda, m0, M, kz0, tid);
   ab.setup(ldb, n0, N, kz0, tid);
   // KCAT: the second operands' addressing (their own k starts at 0 where the first ends)
-  StageAddr<BM, AK, NTH> aa2;
-  StageAddr<BN, BKM, NTH> ab2;
+  StageAddr<BM, AK> aa2;
+  StageAddr<BN, BKM> ab2;
   __amdgpu_buffer_rsrc_t rsa2 = rsa, rsb2 = rsb;
   uint32_t a2_kstride = 0, b2_kstride = 0;
   if constexpr (KCAT) {
@@ -458,7 +436,7 @@ __device__ __forceinline__ void x3_tile(
     aa2.setup(cat.lda2, m0, M, 0, tid);
     ab2.setup(cat.ldb2, n0, N, 0, tid);
   }
-  auto load_a = [&](Stage<BM, AK, NTH>& st, int kt) {
+  auto load_a = [&](Stage<BM, AK>& st, int kt) {
     if constexpr (KCAT) {
       st.load_cat(aa, aa2, rsa, rsa2, (uint32_t)(kt - kz0) * a_kstride, (uint32_t)(kt - cat.kcat) * a2_kstride,
                   cat.kcat, kt, kz1);
@@ -466,7 +444,7 @@ __device__ __forceinline__ void x3_tile(
       st.load(aa, rsa, (uint32_t)(kt - kz0) * a_kstride, kt, kz1);
     }
   };
-  auto load_b = [&](Stage<BN, BKM, NTH>& st, int kt) {
+  auto load_b = [&](Stage<BN, BKM>& st, int kt) {
     if constexpr (KCAT) {
       st.load_cat(ab, ab2, rsb, rsb2, (uint32_t)(kt - kz0) * b_kstride, (uint32_t)(kt - cat.kcat) * b2_kstride,
                   cat.kcat, kt, kz1);
@@ -474,13 +452,9 @@ __device__ __forceinline__ void x3_tile(
       st.load(ab, rsb, (uint32_t)(kt - kz0) * b_kstride, kt, kz1);
     }
   };
-#else
-  auto load_a = [&](Stage<BM, AK, NTH>& st, int kt) { st.load(A, lda, m0, M, kt, kz1, tid); };
-  auto load_b = [&](Stage<BN, BKM, NTH>& st, int kt) { st.load(B, ldb, n0, N, kt, kz1, tid); };
-#endif
-  double rs[Stage<BM, AK, NTH>::RSN];
+  double rs[Stage<BM, AK>::RSN];
 #pragma unroll
-  for (int i = 0; i < Stage<BM, AK, NTH>::RSN; ++i) rs[i] = 0.0;
+  for (int i = 0; i < Stage<BM, AK>::RSN; ++i) rs[i] = 0.0;
 
   const int nk = kz1 > kz0 ? (kz1 - kz0 + KS - 1) / KS : 0;
   const int ra = wm * (BM / 2) + l32, rb = wn * (BN / WN) + l32;
@@ -512,8 +486,8 @@ __device__ __forceinline__ void x3_tile(
     // loads are unconditional) into the slot tile t left, and stores tile t + 1. Measured
     // on the cfg2 step: GEMM 916 -> 902 us (the split waits for a tile issued a step
     // earlier instead of during the same step's MFMAs)
-    Stage<BM, AK, NTH> sa2;
-    Stage<BN, BKM, NTH> sb2;
+    Stage<BM, AK> sa2;
+    Stage<BN, BKM> sb2;
     load_a(sa, kz0);
     load_b(sb, kz0);
     const int k1c = kz0 + min(1, nk - 1) * KS;
@@ -525,7 +499,7 @@ __device__ __forceinline__ void x3_tile(
     __syncthreads();
     // loads sit outside every branch (only MFMAs and stores are conditional), so the
     // compiler's wait counts stay exact across the loop
-    auto kstep = [&](int t, Stage<BM, AK, NTH>& la, Stage<BN, BKM, NTH>& lb, Stage<BM, AK, NTH>& na, Stage<BN, BKM, NTH>& nb) {
+    auto kstep = [&](int t, Stage<BM, AK>& la, Stage<BN, BKM>& lb, Stage<BM, AK>& na, Stage<BN, BKM>& nb) {
       const int cur = t & 1;
       const int kl = kz0 + min(t + 2, nk - 1) * KS;
       load_a(la, kl);
@@ -584,9 +558,9 @@ __device__ __forceinline__ void x3_tile(
   if (do_rs) {
     double* red = reinterpret_cast<double*>(lds);
     if constexpr (!AK) {
-      // row image: unit i of thread tid is row (tid + i NTH) / 4, k-quarter tid % 4
+      // row image: unit i of thread tid is row (tid + i NT) / 4, k-quarter tid % 4
 #pragma unroll
-      for (int i = 0; i < Stage<BM, AK, NTH>::RSN; ++i) red[tid + i * NTH] = rs[i];  // = 4 row + k-quarter
+      for (int i = 0; i < Stage<BM, AK>::RSN; ++i) red[tid + i * NT] = rs[i];  // = 4 row + k-quarter
       __syncthreads();
       if (tid < BM && m0 + tid < M) {
         const double t = (red[4 * tid] + red[4 * tid + 1]) + (red[4 * tid + 2] + red[4 * tid + 3]);
@@ -595,7 +569,7 @@ __device__ __forceinline__ void x3_tile(
       }
     } else {
       // k image: thread tid holds rows 4 (tid % (BM / 4)) .. + 3 for the k-rows tid / (BM / 4)
-      constexpr int G = NTH / (BM / 4);
+      constexpr int G = NT / (BM / 4);
 #pragma unroll
       for (int e = 0; e < 4; ++e) red[(tid / (BM / 4)) * BM + 4 * (tid % (BM / 4)) + e] = rs[e];
       __syncthreads();
@@ -610,20 +584,13 @@ __device__ __forceinline__ void x3_tile(
   }
 
   X3_STAMP(65, 0);
-  x3_store<BM, BN, EPI, PASSES, NTH, RL>(acc, reinterpret_cast<float*>(lds), tid, m0, n0, M, N, kz, alpha, beta, C,
-                                         ldc, bias, slope, dact, lddact, ws, rows);
+  x3_store<BM, BN, EPI, PASSES, RL>(acc, reinterpret_cast<float*>(lds), tid, m0, n0, M, N, kz, alpha, beta, C, ldc,
+                                    bias, slope, dact, lddact, ws, rows);
   X3_STAMP(65, 1);
 }
 
-// XCD-aware order over `items` (slice-major within a product): workgroup b runs on XCD
-// b % 8, which takes one contiguous range of the items, so the workgroups sharing a K
-// slice's operand rows share that XCD's L2 (as gemm.hip's DMA kernel)
-__device__ __forceinline__ int x3_item(int items) {
-  const int b = blockIdx.x;
-  const int q8 = items / 8, r8 = items % 8, x8 = b % 8;
-  return (x8 < r8 ? x8 * (q8 + 1) : r8 * (q8 + 1) + (x8 - r8) * q8) + b / 8;
-}
-
+// Every kernel below takes its work item from xcd_item (gemm_common.hpp): the workgroups
+// sharing a K slice's operand rows share an XCD's L2 (as gemm.hip's DMA kernel).
 template <int BM, int BN, bool TA, bool TB, int EPI>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(x3_waves<BM, BN>())))
 void gemm_x3_kernel(
@@ -633,7 +600,7 @@ void gemm_x3_kernel(
     const float* __restrict__ dact, int64_t lddact, float* __restrict__ rowsum,
     float* __restrict__ ws, float* __restrict__ ws_rowsum, int n_split) {
   __shared__ __attribute__((aligned(16))) uint16_t lds[x3_lds_u16<BM, BN>()];
-  const int item = x3_item(tiles * n_split);
+  const int item = xcd_item(tiles * n_split);
   const int kz = item / tiles, tile = item % tiles;
   x3_tile<BM, BN, TA, TB, EPI>(lds, M, N, K, k_per_split, kz, tile / tiles_n, tile % tiles_n, alpha, A, lda, B,
                                ldb, beta, C, ldc, bias, slope, dact, lddact, rowsum, ws, ws_rowsum);
@@ -648,7 +615,7 @@ void gemm_x3_cat_kernel(
     float* __restrict__ C, int64_t ldc, const float* __restrict__ bias, float slope,
     const float* __restrict__ dact, int64_t lddact, X3Cat cat) {
   __shared__ __attribute__((aligned(16))) uint16_t lds[x3_lds_u16<BM, BN>()];
-  const int tile = x3_item(tiles);
+  const int tile = xcd_item(tiles);
   x3_tile<BM, BN, TA, TB, EPI, true>(lds, M, N, K, K, 0, tile / tiles_n, tile % tiles_n, alpha, A, lda, B, ldb, beta, C,
                                      ldc, bias, slope, dact, lddact, nullptr, nullptr, nullptr, cat);
 }
@@ -661,147 +628,100 @@ void gemm_x3_rows_kernel(
     const float* __restrict__ B, int64_t ldb, float* __restrict__ C, int64_t ldc,
     const int32_t* __restrict__ rows, int m_full) {
   __shared__ __attribute__((aligned(16))) uint16_t lds[x3_lds_u16<BM, BN>()];
-  const int tile = x3_item(tiles);
-  x3_tile<BM, BN, false, TB, EPI_NONE, false, NT, true>(lds, M, N, K, K, 0, tile / tiles_n, tile % tiles_n, 1.f, A, lda,
-                                                        B, ldb, 0.f, C, ldc, nullptr, 0.f, nullptr, 0, nullptr, nullptr,
-                                                        nullptr, X3Cat{}, rows, m_full);
+  const int tile = xcd_item(tiles);
+  x3_tile<BM, BN, false, TB, EPI_NONE, false, true>(lds, M, N, K, K, 0, tile / tiles_n, tile % tiles_n, 1.f, A, lda,
+                                                    B, ldb, 0.f, C, ldc, nullptr, 0.f, nullptr, 0, nullptr, nullptr,
+                                                    nullptr, X3Cat{}, rows, m_full);
 }
 
 // Grouped split-K partials: the items of every part (its tiles x its K slices, slice-major)
 // laid end to end, one launch for all of them (the step's weight gradients: the slab bytes
 // then scale with the group's workgroups, not with each product's).
-#ifndef PG_X3_GROUP_THREADS
-#define PG_X3_GROUP_THREADS 256  // variant builds: 512 = 2 x 4 waves of 64 x 64 per 128 x 256 tile
-#endif
-#ifndef PG_X3_GROUP_WAVES
-#define PG_X3_GROUP_WAVES (PG_X3_GROUP_THREADS == 512 ? 4 : x3_waves<BM, BN>())
-#endif
 template <int BM, int BN, bool TA, bool TB>
-__global__ __launch_bounds__(PG_X3_GROUP_THREADS) __attribute__((amdgpu_waves_per_eu(PG_X3_GROUP_WAVES)))
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(x3_waves<BM, BN>())))
 void gemm_x3_group_kernel(X3Group g) {
   __shared__ __attribute__((aligned(16))) uint16_t lds[x3_lds_u16<BM, BN>()];
-  const int item = x3_item(g.items);
-  int k = 0;
-  while (k + 1 < g.n && item >= g.p[k + 1].first_item) ++k;
-  const X3Part& p = g.p[k];
+  const int item = xcd_item(g.items);
+  const GemmPart<float>& p = group_part(g, item);
   const int local = item - p.first_item;
   const int kz = local / p.tiles, tile = local % p.tiles;
-  x3_tile<BM, BN, TA, TB, EPI_SPLIT, false, PG_X3_GROUP_THREADS>(lds, p.M, p.N, p.K, p.kps, kz, tile / p.tiles_n,
-                                                                 tile % p.tiles_n, 1.f, p.A,
-                                     p.lda, p.B, p.ldb, 0.f, nullptr, 0, nullptr, 0.f, nullptr, 0, p.rowsum, p.ws,
-                                     p.ws_rowsum);
-}
-
-
-
-template <int BM, int BN, bool TA, bool TB>
-int launch_epi(const X3Args& a, hipStream_t st) {
-  const dim3 grid((unsigned)(a.tiles * a.n_split)), block(NT);
-#define PG_L(EPI_)                                                                                   \
-  hipLaunchKernelGGL((gemm_x3_kernel<BM, BN, TA, TB, EPI_>), grid, block, 0, st, a.M, a.N, a.K, a.kps, \
-                     a.tiles_n, a.tiles, a.alpha, a.A, a.lda, a.B, a.ldb, a.beta, a.C, a.ldc, a.bias,   \
-                     a.slope, a.dact, a.lddact, a.rowsum, a.ws, a.ws_rowsum, a.n_split)
-  switch (a.epi) {
-    case EPI_NONE: PG_L(EPI_NONE); break;
-    case EPI_RELU: PG_L(EPI_RELU); break;
-    case EPI_LEAKY: PG_L(EPI_LEAKY); break;
-    case EPI_DRELU: PG_L(EPI_DRELU); break;
-    case EPI_DLEAKY: PG_L(EPI_DLEAKY); break;
-    case EPI_SPLIT: PG_L(EPI_SPLIT); break;
-    default: return PG_ERR_INVALID;
-  }
-#undef PG_L
-  return PG_OK;
-}
-
-template <int BM, int BN>
-int launch_trans(const X3Args& a, hipStream_t st) {
-  if (!a.ta && !a.tb) return launch_epi<BM, BN, false, false>(a, st);
-  if (!a.ta && a.tb) return launch_epi<BM, BN, false, true>(a, st);
-  if (a.ta && !a.tb) return launch_epi<BM, BN, true, false>(a, st);
-  return launch_epi<BM, BN, true, true>(a, st);
+  x3_tile<BM, BN, TA, TB, EPI_SPLIT>(lds, p.M, p.N, p.K, p.kps, kz, tile / p.tiles_n, tile % p.tiles_n, 1.f, p.A, p.lda,
+                                     p.B, p.ldb, 0.f, nullptr, 0, nullptr, 0.f, nullptr, 0, p.rowsum, p.ws, p.ws_rowsum);
 }
 
 }  // namespace
 
 namespace pg_gemm {
 
+// the tiles of every launcher below: a kernel is built where x3_tile_built says
+// pick_tile_x3 can return the tile
+template <class F>
+int dispatch_x3_tile(int bm, int bn, F&& f, int miss = PG_ERR_INVALID) {
+  return dispatch_tile<Tile<128, 128>, Tile<128, 64>, Tile<64, 128>, Tile<64, 64>>(bm, bn, f, miss);
+}
+
+int gemm_x3_launch(const X3Args& a, hipStream_t st) {
+  return dispatch_x3_tile(a.bm, a.bn, [&](auto tile) {
+    return dispatch_flags(a.ta, a.tb, [&](auto ta, auto tb) {
+      return dispatch_epi(a.epi, [&](auto epi) {
+        constexpr int BM = decltype(tile)::bm, BN = decltype(tile)::bn, EPI = decltype(epi)::value;
+        if constexpr (!x3_tile_built<BM, BN>(EPI == EPI_SPLIT)) {
+          return (int)PG_ERR_INVALID;
+        } else {
+          hipLaunchKernelGGL((gemm_x3_kernel<BM, BN, decltype(ta)::value, decltype(tb)::value, EPI>),
+                             dim3((unsigned)(a.tiles * a.n_split)), dim3(NT), 0, st, a.M, a.N, a.K, a.kps, a.tiles_n,
+                             a.tiles, a.alpha, a.A, a.lda, a.B, a.ldb, a.beta, a.C, a.ldc, a.bias, a.slope, a.dact,
+                             a.lddact, a.rowsum, a.ws, a.ws_rowsum, a.n_split);
+          return (int)PG_OK;
+        }
+      });
+    });
+  });
+}
+
 int gemm_x3_group_launch(const X3Group& g, bool ta, bool tb, hipStream_t st) {
-  const dim3 grid((unsigned)g.items), block(PG_X3_GROUP_THREADS);
-#define PG_G(TA_, TB_) \
-  hipLaunchKernelGGL((gemm_x3_group_kernel<kX3GroupBM, kX3GroupBN, TA_, TB_>), grid, block, 0, st, g)
-  if (ta && !tb) PG_G(true, false);
-  else if (!ta && !tb) PG_G(false, false);
-  else if (!ta && tb) PG_G(false, true);
-  else PG_G(true, true);
-#undef PG_G
-  return PG_OK;
+  return dispatch_flags(ta, tb, [&](auto ta_, auto tb_) {
+    hipLaunchKernelGGL((gemm_x3_group_kernel<kX3GroupBM, kX3GroupBN, decltype(ta_)::value, decltype(tb_)::value>),
+                       dim3((unsigned)g.items), dim3(NT), 0, st, g);
+    return (int)PG_OK;
+  });
 }
 
-#if PG_X3_BUFLOAD
-template <int BM, int BN>
-int launch_cat(const X3Args& a, const X3Cat& c, hipStream_t st) {
-  if (a.ta || (a.epi != EPI_NONE && a.epi != EPI_LEAKY)) return PG_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)a.tiles), block(NT);
-#define PG_C(TB_, EPI_)                                                                                  \
-  hipLaunchKernelGGL((gemm_x3_cat_kernel<BM, BN, false, TB_, EPI_>), grid, block, 0, st, a.M, a.N, a.K, \
-                     a.tiles_n, a.tiles, a.alpha, a.A, a.lda, a.B, a.ldb, a.beta, a.C, a.ldc, a.bias, a.slope, \
-                     a.dact, a.lddact, c)
-  if (a.tb) {
-    if (a.epi == EPI_NONE) PG_C(true, EPI_NONE); else PG_C(true, EPI_LEAKY);
-  } else {
-    if (a.epi == EPI_NONE) PG_C(false, EPI_NONE); else PG_C(false, EPI_LEAKY);
-  }
-#undef PG_C
-  return PG_OK;
-}
-
+// PG_ERR_UNSUPPORTED for a tile with no cat instantiation: the caller concatenates
 int gemm_x3_cat_launch(const X3Args& a, const float* A2, int64_t lda2, const float* B2, int64_t ldb2, int kcat,
                        hipStream_t st) {
   const X3Cat c{A2, lda2, B2, ldb2, kcat};
-  if (a.bm == 128 && a.bn == 128) return launch_cat<128, 128>(a, c, st);
-  if (a.bm == 128 && a.bn == 64) return launch_cat<128, 64>(a, c, st);
-  if (a.bm == 64 && a.bn == 128) return launch_cat<64, 128>(a, c, st);
-  if (a.bm == 64 && a.bn == 64) return launch_cat<64, 64>(a, c, st);
-  return PG_ERR_UNSUPPORTED;  // a tile with no cat instantiation: the caller concatenates
-}
-#else
-int gemm_x3_cat_launch(const X3Args&, const float*, int64_t, const float*, int64_t, int, hipStream_t) {
-  return PG_ERR_UNSUPPORTED;
-}
-#endif
-
-#if PG_X3_BUFLOAD
-template <int BM, int BN>
-int launch_rows(const X3Args& a, const int32_t* rows, int m_full, hipStream_t st) {
-  const dim3 grid((unsigned)a.tiles), block(NT);
-  if (a.tb)
-    hipLaunchKernelGGL((gemm_x3_rows_kernel<BM, BN, true>), grid, block, 0, st, a.M, a.N, a.K, a.tiles_n, a.tiles,
-                       a.A, a.lda, a.B, a.ldb, a.C, a.ldc, rows, m_full);
-  else
-    hipLaunchKernelGGL((gemm_x3_rows_kernel<BM, BN, false>), grid, block, 0, st, a.M, a.N, a.K, a.tiles_n, a.tiles,
-                       a.A, a.lda, a.B, a.ldb, a.C, a.ldc, rows, m_full);
-  return PG_OK;
+  if (a.ta || (a.epi != EPI_NONE && a.epi != EPI_LEAKY)) return PG_ERR_UNSUPPORTED;
+  return dispatch_x3_tile(a.bm, a.bn, [&](auto tile) {
+    return dispatch_flags(a.tb, a.epi == EPI_LEAKY, [&](auto tb, auto leaky) {
+      constexpr int BM = decltype(tile)::bm, BN = decltype(tile)::bn;
+      constexpr int EPI = decltype(leaky)::value ? EPI_LEAKY : EPI_NONE;
+      if constexpr (!x3_tile_built<BM, BN>(false)) {
+        return (int)PG_ERR_UNSUPPORTED;
+      } else {
+        hipLaunchKernelGGL((gemm_x3_cat_kernel<BM, BN, false, decltype(tb)::value, EPI>), dim3((unsigned)a.tiles),
+                           dim3(NT), 0, st, a.M, a.N, a.K, a.tiles_n, a.tiles, a.alpha, a.A, a.lda, a.B, a.ldb, a.beta,
+                           a.C, a.ldc, a.bias, a.slope, a.dact, a.lddact, c);
+        return (int)PG_OK;
+      }
+    });
+  }, PG_ERR_UNSUPPORTED);
 }
 
 int gemm_x3_rows_launch(const X3Args& a, const int32_t* rows, int m_full, hipStream_t st) {
   if (a.ta || a.epi != EPI_NONE || a.n_split != 1) return PG_ERR_UNSUPPORTED;
-  if (a.bm == 128 && a.bn == 128) return launch_rows<128, 128>(a, rows, m_full, st);
-  if (a.bm == 128 && a.bn == 64) return launch_rows<128, 64>(a, rows, m_full, st);
-  if (a.bm == 64 && a.bn == 128) return launch_rows<64, 128>(a, rows, m_full, st);
-  if (a.bm == 64 && a.bn == 64) return launch_rows<64, 64>(a, rows, m_full, st);
-  return PG_ERR_UNSUPPORTED;
-}
-#else
-int gemm_x3_rows_launch(const X3Args&, const int32_t*, int, hipStream_t) { return PG_ERR_UNSUPPORTED; }
-#endif
-
-int gemm_x3_launch(const X3Args& a, hipStream_t st) {
-  if (a.bm == 128 && a.bn == 128) return launch_trans<128, 128>(a, st);
-  if (a.bm == 128 && a.bn == 64) return launch_trans<128, 64>(a, st);
-  if (a.bm == 64 && a.bn == 128) return launch_trans<64, 128>(a, st);
-  if (a.bm == 64 && a.bn == 64) return launch_trans<64, 64>(a, st);
-  return PG_ERR_INVALID;
+  return dispatch_x3_tile(a.bm, a.bn, [&](auto tile) {
+    return dispatch_flag(a.tb, [&](auto tb) {
+      constexpr int BM = decltype(tile)::bm, BN = decltype(tile)::bn;
+      if constexpr (!x3_tile_built<BM, BN>(false)) {
+        return (int)PG_ERR_UNSUPPORTED;
+      } else {
+        hipLaunchKernelGGL((gemm_x3_rows_kernel<BM, BN, decltype(tb)::value>), dim3((unsigned)a.tiles), dim3(NT), 0,
+                           st, a.M, a.N, a.K, a.tiles_n, a.tiles, a.A, a.lda, a.B, a.ldb, a.C, a.ldc, rows, m_full);
+        return (int)PG_OK;
+      }
+    });
+  }, PG_ERR_UNSUPPORTED);
 }
 
 }  // namespace pg_gemm

@@ -7,13 +7,17 @@ One line per kernel and code object: mangled name, code size in bytes, SHA-256 o
 function's bytes in .text followed by its 64-byte kernel descriptor (the <name>.kd symbol).
 The descriptor's kernel_code_entry_byte_offset (bytes 16-23: the distance from the descriptor
 to the code, which moves with the kernel's place in the file) is hashed as zero; everything
-else is the raw bytes. A kernel that calls a function it did not inline would differ in the
-call's PC-relative offset when the layout changes; none of this library's does.
+else is the raw bytes, but for the PC-relative address of a global (s_getpc_b64 s[n:n+1];
+s_add_u32 sn, sn, literal; s_addc_u32 sn+1, sn+1, literal: the distance from the instruction
+to the global, which moves with the kernel's place in the file as well): both literals are
+hashed as zero. A kernel that calls a function it did not inline would differ in the call's
+PC-relative offset when the layout changes; none of this library's does.
 Needs only the ROCm LLVM tools (llvm-objcopy, clang-offload-bundler, llvm-readelf,
 llvm-objdump); opens no GPU. A comparison aid, not a test.
 """
 import hashlib
 import os
+import struct
 import subprocess
 import sys
 import tempfile
@@ -43,6 +47,20 @@ def code_objects(path, tmp):
         yield co
 
 
+def mask_pcrel(code):
+    """The function's bytes with the literals of every PC-relative global address zeroed."""
+    w = list(struct.unpack("<%dI" % (len(code) // 4), code[:len(code) // 4 * 4]))
+    for i in range(len(w) - 4):
+        if w[i] & 0xFF80FFFF != 0xBE801C00:  # s_getpc_b64 s[n:n+1]
+            continue
+        n = (w[i] >> 16) & 0x7F
+        lo = 0x8000FF00 | n << 16 | n  # s_add_u32 sn, sn, literal
+        hi = 0x8200FF00 | (n + 1) << 16 | (n + 1)  # s_addc_u32 sn+1, sn+1, literal
+        if w[i + 1] == lo and w[i + 3] == hi:
+            w[i + 2] = w[i + 4] = 0
+    return struct.pack("<%dI" % len(w), *w) + code[len(w) * 4:]
+
+
 def kernels(co):
     """(name, size, digest) of every function of the code object that has a kernel descriptor."""
     sec = {}  # section name -> (address, file offset)
@@ -66,7 +84,7 @@ def kernels(co):
         if name + ".kd" in sym and sym[name][1] == ".text":
             kd = bytearray(raw(name + ".kd", 64))
             kd[16:24] = bytes(8)
-            yield name, sym[name][2], hashlib.sha256(raw(name) + bytes(kd)).hexdigest()
+            yield name, sym[name][2], hashlib.sha256(mask_pcrel(raw(name)) + bytes(kd)).hexdigest()
 
 
 def main(paths):

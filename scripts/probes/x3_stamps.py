@@ -1,5 +1,5 @@
 """Per-step clock stamps of the register-staged three-piece GEMM (probe build:
-make variant V=stamp VSRC=gemm_x3 VFLAGS="-fno-slp-vectorize -DPG_X3_DMA=0 -DPG_X3_STAMP=1").
+make variant V=stamp VSRC=gemm_x3 VFLAGS=-DPG_X3_STAMP=1).
 Prints, for blocks 0..63 (wave 0), the median cycles of each step phase: load+frag+MFMA
 issue, the wait for the next tile's global loads, split+store; and the prologue / epilogue.
 Usage: PLAGNN_LIB=.../libplagnn_stamp.so python scripts/probes/x3_stamps.py M N K ta tb"""
