@@ -36,6 +36,9 @@
  *   pg_sample_fill,         dgl.to_block (include_dst_in_src): the per-batch work of a sampled mini-batch
  *   pg_block_compact        loop (dgl.dataloading.NeighborSampler). Not used by the reference, which trains
  *                           the full graph: reference-unpinned.
+ *   pg_csr_transpose_dev,   <- the same loop: each sampled block's reverse CSR and both work schedules,
+ *   pg_schedule_count_dev,     built where the block was sampled (the device twins of pg_csr_transpose /
+ *   pg_schedule_build_dev      pg_schedule_*). Reference-unpinned.
  *   pg_argpos_to_src     <- DGL's argX (source node id of the max) from our compact
  *                           per-row edge positions
  *   pg_sigmoid_multi_loss<- th.sigmoid (code/model.py:29) + multi_loss
@@ -74,7 +77,8 @@
  *     they never allocate, copy to host or synchronise, so they can be captured
  *     into a HIP graph. Scratch comes from the caller through (ws, ws_bytes),
  *     sized by the matching *_workspace() query.
- *   - Host entry points (pg_csr_*, pg_schedule_*) take host pointers.
+ *   - Host entry points (pg_csr_*, pg_schedule_*) take host pointers; their twins suffixed _dev
+ *     are device entry points.
  *   - Dense matrices are row-major with an explicit leading dimension (elements).
  *   - Return 0 on success, a negative PG_ERR_* code for an argument error, or a
  *     positive hipError_t for a launch error. pg_last_error_string() gives a
@@ -422,6 +426,44 @@ size_t pg_block_compact_workspace(int64_t n_dst, int64_t nnz, int64_t n_parent);
 int pg_block_compact(const int32_t* dst_ids, int64_t n_dst, const int32_t* col, int64_t nnz,
                      int64_t n_parent, int32_t* src_ids, int32_t* col_local, int32_t* n_src_dev,
                      void* ws, size_t ws_bytes, pg_stream_t stream);
+
+/* A sampled block's transpose and schedules on the device: the twins of the host entry points
+ * pg_csr_transpose / pg_schedule_count / pg_schedule_build on device pointers, equal to them bit
+ * for bit (the host functions are the specification), so that dgl.dataloading.NeighborSampler
+ * moves no index array across the bus. They follow the device contract above: enqueue on
+ * `stream`, scratch through (ws, ws_bytes), nothing allocated, copied to the host or
+ * synchronised (each can be captured), an argument error launches nothing. All three succeed
+ * and read no input buffer when there are no rows, no columns or no entries. No atomics: every
+ * result is a function of the arguments. Core: a stable LSD radix sort of (key, value) u32
+ * pairs, 8-bit digits, 1024 entries per workgroup; a pass = per-tile digit counts, a scan of the
+ * (digit-major, tile-minor) table, a stable scatter whose ranks inside a tile come from wave
+ * ballots and a cross-wave prefix in LDS.
+ *
+ * pg_csr_transpose_dev: tslot = the slots sorted stably by column over
+ *   ceil(bits(n_cols - 1) / 8) passes (row ids ascending in each transposed row, duplicates in
+ *   slot order), tptr[c] = the first sorted position whose column is >= c, tcol[t] = the row of
+ *   tslot[t] (binary search in ptr), tpos[t] = tslot[t] - ptr[tcol[t]] (tslot, tpos may be
+ *   NULL). *status_dev (int32, device) = 0, -2 when a col[k] lies outside [0, n_cols) (it is
+ *   then taken as column 0: nothing is indexed with it), -3 when ptr does not span nnz; the
+ *   outputs are then unspecified but every access stays inside the buffers.
+ * pg_schedule_count_dev: counts_dev[6] (int64, device) = n_items, n_merges, n_slots, max_deg,
+ *   min_deg (0 without rows), status (-1: ptr not monotone, -2: a total reaches 2^31).
+ * pg_schedule_build_dev: items[4 n_items], merges[4 n_merges] in pg_schedule_build's order.
+ *   n_items, n_merges and max_deg are the count's, read back by the caller; every write is
+ *   guarded by them. Raw item indices and slots come from exclusive scans over the rows; items
+ *   are sorted stably by chunk - len over bits(chunk) key bits, merges by
+ *   ceil(max_deg / chunk) - n, both with the raw index as value. */
+size_t pg_csr_transpose_dev_workspace(int64_t n_rows, int64_t n_cols, int64_t nnz);
+int pg_csr_transpose_dev(const int32_t* ptr, const int32_t* col, int64_t n_rows, int64_t n_cols,
+                         int64_t nnz, int32_t* tptr, int32_t* tcol, int32_t* tslot, int32_t* tpos,
+                         int32_t* status_dev, void* ws, size_t ws_bytes, pg_stream_t stream);
+size_t pg_schedule_count_dev_workspace(int64_t n_rows);
+int pg_schedule_count_dev(const int32_t* ptr, int64_t n_rows, int32_t chunk, int64_t* counts_dev,
+                          void* ws, size_t ws_bytes, pg_stream_t stream);
+size_t pg_schedule_build_dev_workspace(int64_t n_rows, int64_t n_items, int64_t n_merges);
+int pg_schedule_build_dev(const int32_t* ptr, int64_t n_rows, int32_t chunk, int64_t n_items,
+                          int64_t n_merges, int32_t max_deg, int32_t* items, int32_t* merges,
+                          void* ws, size_t ws_bytes, pg_stream_t stream);
 
 /* ---------------- device: dense helpers of the training step ---------------- */
 
@@ -828,7 +870,10 @@ int pg_version(void); /* 2: pg_csr_t.einv; 3: pg_spmm_max_bwd fwd_out; 5: no in-
                          the _cpu twins of the first two (fused GATv2 attention scores);
                          13 also: pg_sample_count, pg_sample_fill,
                          pg_block_compact, their workspace queries and _cpu twins
-                         (neighbour sampling and block compaction) */
+                         (neighbour sampling and block compaction);
+                         13 also: pg_csr_transpose_dev, pg_schedule_count_dev,
+                         pg_schedule_build_dev and their workspace queries (a sampled
+                         block's transpose and schedules on the device) */
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@
 // pg_block_compact dense first-position map over the parent's ids (int32 atomicMin: the minimum
 //                  of a set of integers does not depend on the order they arrive in), flags of
 //                  the first appearances, one prefix sum, two gathers.
-// Prefix sums: 1024 elements per workgroup, the workgroup totals scanned by one workgroup.
+// Prefix sums: scan.hpp (1024 elements per workgroup, the workgroup totals scanned by one workgroup).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -22,71 +22,13 @@
 
 #include "common.hpp"
 #include "sample_key.hpp"
+#include "scan.hpp"
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr int kBlock = 256;
-constexpr int kWavesPerBlock = kBlock / kWave;
-constexpr int kPerThread = 4;
-constexpr int kTile = kBlock * kPerThread;  // elements of one workgroup's local scan
 constexpr int kCap = PG_SAMPLE_LDS_KEYS;
 constexpr int kCand = kCap / 2;  // (key, position) candidates of a hub row in the same LDS
 constexpr int32_t kNever = INT32_MAX;
-
-inline int64_t tiles_of(int64_t n) { return (n + kTile - 1) / kTile; }
-inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
-// exclusive scan of one value per thread over the workgroup; *total = the workgroup's sum
-__device__ inline int block_excl_scan(int v, int* lds, int* total) {
-  const int t = threadIdx.x;
-  lds[t] = v;
-  __syncthreads();
-  for (int off = 1; off < kBlock; off <<= 1) {
-    const int add = t >= off ? lds[t - off] : 0;
-    __syncthreads();
-    lds[t] += add;
-    __syncthreads();
-  }
-  const int incl = lds[t];
-  *total = lds[kBlock - 1];
-  __syncthreads();
-  return incl - v;
-}
-
-// v[0..4) of this thread -> local exclusive offsets written to out[i0 .. i0+4), tile total
-__device__ inline void tile_scan_store(const int (&v)[kPerThread], int64_t i0, int64_t n, int32_t* out,
-                                       int32_t* tile_sums, int* lds) {
-  int sum = 0;
-  for (int q = 0; q < kPerThread; ++q) sum += v[q];
-  int total;
-  int run = block_excl_scan(sum, lds, &total);
-  for (int q = 0; q < kPerThread; ++q) {
-    if (i0 + q < n) out[i0 + q] = run;
-    run += v[q];
-  }
-  if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
-}
-
-// one workgroup: tile_sums -> their exclusive scan in place; the grand total to total_out[0]
-// (or, with status: a negative status instead of the total)
-__global__ __launch_bounds__(kBlock) void scan_tiles_kernel(int32_t* tile_sums, int64_t n_tiles, int32_t* total_out,
-                                                            const int32_t* status) {
-  __shared__ int lds[kBlock];
-  int carry = 0;
-  for (int64_t base = 0; base < n_tiles; base += kBlock) {
-    const int64_t i = base + threadIdx.x;
-    const int v = i < n_tiles ? tile_sums[i] : 0;
-    int total;
-    const int ex = block_excl_scan(v, lds, &total);
-    if (i < n_tiles) tile_sums[i] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) {
-    const int32_t st = status ? status[0] : 0;
-    total_out[0] = st < 0 ? st : carry;
-  }
-}
 
 __device__ inline int32_t row_degree(const int32_t* ptr, int64_t n_rows, int32_t s) {
   if (s < 0 || s >= n_rows) return 0;
@@ -109,13 +51,6 @@ __global__ __launch_bounds__(kBlock) void sample_count_kernel(const int32_t* ptr
     v[q] = d;
   }
   tile_scan_store(v, i0, n_seeds, out_ptr, tile_sums, lds);
-}
-
-__global__ __launch_bounds__(kBlock) void add_tile_offsets_kernel(int32_t* out, int64_t n, const int32_t* tile_offs) {
-  const int64_t i0 = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * kPerThread;
-  const int32_t off = tile_offs[blockIdx.x];
-  for (int q = 0; q < kPerThread; ++q)
-    if (i0 + q < n) out[i0 + q] += off;
 }
 
 __global__ __launch_bounds__(kBlock) void sample_fill_kernel(const int32_t* __restrict__ ptr,

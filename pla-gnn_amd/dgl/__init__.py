@@ -500,7 +500,8 @@ class DGLBlock(DGLGraph):
     nodes, edges src -> dst in local ids (edge id = position), separate srcdata / dstdata
     frames. With include_dst_in_src (the only form built here) the first num_dst source nodes
     are the destination nodes. The engine graph is rectangular (CSRGraph.from_coo_rect, or the
-    sampler's finished in-CSR through CSRGraph.from_in_csr)."""
+    sampler's finished in-CSR through DeviceGraph.from_in_csr on a HIP device, CSRGraph.from_in_csr
+    on the host)."""
 
     is_block = True
 
@@ -606,6 +607,18 @@ def _block_from_in_csr(ptr, col_local, num_src: int, device) -> DGLBlock:
     cache = {"host": _engine().CSRGraph.from_in_csr(ptr, col_local, num_src)}
     return DGLBlock(torch.from_numpy(col_local.astype(_np.int64)), torch.from_numpy(dst), num_src, num_dst,
                     device=device, _csr_cache=cache)
+
+
+def _block_from_device_csr(ptr, col_local, num_src: int) -> DGLBlock:
+    """A block from a finished in-CSR on a HIP device (int32 tensors; edge id = slot): its engine
+    graph is built there (plagnn.graph.DeviceBuiltGraph), and so are the block's COO arrays; no
+    index array crosses the bus."""
+    dev = ptr.device
+    num_dst, total = ptr.numel() - 1, col_local.numel()
+    dst = torch.repeat_interleave(torch.arange(num_dst, dtype=torch.int64, device=dev), ptr.diff().to(torch.int64),
+                                  output_size=total)  # output_size: no synchronising read of the sum
+    cache = {"host": _engine().graph.DeviceBuiltGraph(ptr, col_local, num_src)}
+    return DGLBlock(col_local.to(torch.int64), dst, num_src, num_dst, device=dev, _csr_cache=cache)
 
 
 def to_block(g: DGLGraph, dst_nodes=None, include_dst_in_src: bool = True) -> DGLBlock:

@@ -1,8 +1,11 @@
 """dgl.dataloading: multi-layer neighbour samplers that return blocks, and a minimal
 single-process DataLoader over node ids. Choosing the neighbours (pg_sample_count /
-pg_sample_fill) and relabelling them (pg_block_compact) run on the graph's device; per block
-the host reads the sampled ptr and the local column ids back once and builds the transpose
-and the work schedules (CSRGraph.from_in_csr)."""
+pg_sample_fill) and relabelling them (pg_block_compact) run on the graph's device. On a HIP
+device each block's transpose and work schedules are built there too (DeviceGraph.from_in_csr:
+pg_csr_transpose_dev, pg_schedule_count_dev, pg_schedule_build_dev): per block the host reads
+three small things back (the entry count, the source count, the schedule counts) and no index
+array. On the CPU device, or with plagnn.graph.DEVICE_BUILD = False, the host builds them
+(CSRGraph.from_in_csr)."""
 from __future__ import annotations
 
 import torch
@@ -33,6 +36,7 @@ class NeighborSampler:
         and the list is built back to front, as DGL does. The sampled CSR goes straight to the
         block's engine graph (no COO round trip)."""
         import dgl
+        from plagnn import graph as engine_graph
         from plagnn import ops
 
         from .sampling import _sample_csr
@@ -45,7 +49,10 @@ class NeighborSampler:
         for fanout in reversed(self.fanouts):
             seeds, ptr, col, eid = _sample_csr(g, seeds, fanout)
             src_ids, col_local = ops.block_compact(seeds, col, g.num_nodes())
-            b = dgl._block_from_in_csr(ptr.cpu().numpy(), col_local.cpu().numpy(), src_ids.numel(), g.device)
+            if engine_graph.DEVICE_BUILD and ptr.device.type == "cuda":
+                b = dgl._block_from_device_csr(ptr, col_local, src_ids.numel())
+            else:
+                b = dgl._block_from_in_csr(ptr.cpu().numpy(), col_local.cpu().numpy(), src_ids.numel(), g.device)
             src_ids = src_ids.to(torch.int64)
             b.srcdata[dgl.NID] = src_ids
             b.dstdata[dgl.NID] = seeds

@@ -110,7 +110,7 @@ class SAGEConv(nn.Module):
                 h_neigh = ops.SumAggregate.apply(h, dg, ews, True)
             else:  # gcn: (sum of neighbours + self) / (in-degree + 1)
                 s = ops.SumAggregate.apply(h, dg, ews, False)
-                degs = torch.as_tensor(graph._engine_graph().in_degrees(), device=feat_src.device)
+                degs = dg.in_degrees()
                 if not graph.is_block:
                     h_self = h
                 elif isinstance(feat, tuple):
@@ -162,12 +162,12 @@ class GraphConv(nn.Module):
         feat, _ = _expand(graph, feat)  # only the source features are read; norms are per side
         dg = graph._device_graph(feat.device)
         eg = graph._engine_graph()
-        if not self._allow_zero_in_degree and (eg.in_degrees() == 0).any():
+        if not self._allow_zero_in_degree and eg.has_zero_in_degree():
             raise plagnn.PlagnnError("There are 0-in-degree nodes in the graph; add self-loops "
                                      "or set allow_zero_in_degree=True")
         ews = dg.edge_weight_slots(edge_weight)
         if self._norm in ("left", "both"):
-            degs = torch.as_tensor(eg.out_degrees(), device=feat.device).float().clamp(min=1)
+            degs = dg.out_degrees().float().clamp(min=1)
             norm = torch.pow(degs, -0.5) if self._norm == "both" else 1.0 / degs
             feat = feat * norm.reshape(-1, 1)
         w = weight if weight is not None else self.weight
@@ -180,7 +180,7 @@ class GraphConv(nn.Module):
             if w is not None:
                 rst = rst @ w
         if self._norm in ("right", "both"):
-            degs = torch.as_tensor(eg.in_degrees(), device=feat.device).float().clamp(min=1)
+            degs = dg.in_degrees().float().clamp(min=1)
             norm = torch.pow(degs, -0.5) if self._norm == "both" else 1.0 / degs
             rst = rst * norm.reshape(-1, 1)
         if self.bias is not None:
@@ -247,7 +247,7 @@ class GATConv(nn.Module):
 
         _check_graph(graph)
         with graph.local_scope():
-            if not self._allow_zero_in_degree and (graph._engine_graph().in_degrees() == 0).any():
+            if not self._allow_zero_in_degree and graph._engine_graph().has_zero_in_degree():
                 raise plagnn.PlagnnError("There are 0-in-degree nodes in the graph; add self-loops "
                                          "or set allow_zero_in_degree=True")
             H, out = self._num_heads, self._out_feats
@@ -351,7 +351,7 @@ class GATv2Conv(nn.Module):
 
     def forward(self, graph, feat, get_attention=False):
         _check_graph(graph)
-        if not self._allow_zero_in_degree and (graph._engine_graph().in_degrees() == 0).any():
+        if not self._allow_zero_in_degree and graph._engine_graph().has_zero_in_degree():
             raise plagnn.PlagnnError("There are 0-in-degree nodes in the graph; add self-loops "
                                      "or set allow_zero_in_degree=True")
         H, out = self._num_heads, self._out_feats
@@ -411,7 +411,7 @@ class EdgeConv(nn.Module):
         _check_graph(g)
         h_src, h_dst = _expand(g, feat)
         with g.local_scope():
-            if not self._allow_zero_in_degree and (g._engine_graph().in_degrees() == 0).any():
+            if not self._allow_zero_in_degree and g._engine_graph().has_zero_in_degree():
                 raise plagnn.PlagnnError("There are 0-in-degree nodes in the graph; add self-loops "
                                          "or set allow_zero_in_degree=True")
             g.srcdata["x"] = h_src

@@ -238,6 +238,12 @@ SIGNATURES = {
     "pg_sample_fill": (_i, [_csr, _vp, _vp, _i64, _i32, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
     "pg_block_compact_workspace": (_sz, [_i64, _i64, _i64]),
     "pg_block_compact": (_i, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pg_csr_transpose_dev_workspace": (_sz, [_i64, _i64, _i64]),
+    "pg_csr_transpose_dev": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pg_schedule_count_dev_workspace": (_sz, [_i64]),
+    "pg_schedule_count_dev": (_i, [_vp, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "pg_schedule_build_dev_workspace": (_sz, [_i64, _i64, _i64]),
+    "pg_schedule_build_dev": (_i, [_vp, _i64, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
     "pg_sample_count_cpu": (_i, [_csr, _vp, _i64, _i32, _vp]),
     "pg_sample_fill_cpu": (_i, [_csr, _vp, _vp, _i64, _i32, ctypes.c_uint64, _vp, _vp, _vp]),
     "pg_block_compact_cpu": (_i, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),

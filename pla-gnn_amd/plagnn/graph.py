@@ -9,6 +9,11 @@ C-ABI host entry points (pg_csr_from_coo / pg_csr_transpose / pg_schedule_*).
 Device side: one ``DeviceGraph`` per torch device, uploaded once and cached; int32 ids
 throughout (DGL uses int64), the compact per-row argmax positions are u16 whenever the
 largest in-degree allows (else int32).
+
+A sampled block's in-CSR is born on the device: ``DeviceGraph.from_in_csr`` builds its transpose
+and both schedules there (pg_csr_transpose_dev / pg_schedule_count_dev / pg_schedule_build_dev,
+the twins of the host calls, equal to them bit for bit) with one small read-back of the counts,
+and ``DeviceBuiltGraph`` stands in for the host ``CSRGraph`` until something asks for host arrays.
 """
 from __future__ import annotations
 
@@ -35,6 +40,9 @@ DEFAULT_CHUNK_BWD = None
 CHUNK_BWD_OVERRIDE: Optional[int] = None  # tuning experiments (bench.py --chunk-bwd)
 # graphs from this many edges (self-loops included) get transposed max-backward descriptors
 TRANS_MIN_EDGES = 1 << 22
+# sampled blocks (dgl.dataloading) build their transpose and schedules on the HIP device they
+# were sampled on; False keeps the host build (CSRGraph.from_in_csr + upload) for A/B runs
+DEVICE_BUILD = True
 
 
 def default_chunk_bwd(num_nodes: int) -> int:
@@ -96,6 +104,19 @@ class DeviceCsr:
         self.n_rows, self.n_cols, self.nnz = h.n_rows, h.n_cols, h.nnz
         self.n_items, self.n_merges, self.n_slots = h.n_items, h.n_merges, h.n_slots
         self.max_deg, self.chunk = h.max_deg, h.chunk
+
+    @classmethod
+    def from_tensors(cls, device: torch.device, ptr, col, eslot, epos, items, merges, n_cols: int, n_items: int,
+                     n_merges: int, n_slots: int, max_deg: int, chunk: int) -> "DeviceCsr":
+        """The same object from tensors that already live on `device` (int32; eslot / epos may
+        be None), with the counts the schedule was built with."""
+        c = cls.__new__(cls)
+        c.device = device
+        c.ptr, c.col, c.eslot, c.epos, c.items, c.merges = ptr, col, eslot, epos, items, merges
+        c.n_rows, c.n_cols, c.nnz = int(ptr.numel()) - 1, int(n_cols), int(col.numel())
+        c.n_items, c.n_merges, c.n_slots = int(n_items), int(n_merges), int(n_slots)
+        c.max_deg, c.chunk = int(max_deg), int(chunk)
+        return c
 
     def struct(self, ew: Optional[torch.Tensor] = None) -> PgCsr:
         """The pg_csr_t view (cached per edge-weight pointer: it holds raw pointers only)."""
@@ -235,6 +256,53 @@ class CSRGraph:
     def out_degrees(self) -> np.ndarray:
         return np.diff(self.bwd.ptr)
 
+    def has_zero_in_degree(self) -> bool:
+        return bool((self.in_degrees() == 0).any())
+
+
+def _dev_ws(nbytes: int, device) -> torch.Tensor:
+    from .ops import _workspace  # deferred: ops imports this module
+
+    return _workspace(max(int(nbytes), 256), device)
+
+
+def _schedule_count_dev(ptr: torch.Tensor, chunk: int) -> torch.Tensor:
+    """int64[6] on ptr's device (pg_schedule_count_dev): n_items, n_merges, n_slots, max_deg,
+    min_deg, status. Nothing is read back here."""
+    n_rows = ptr.numel() - 1
+    counts = torch.empty(6, dtype=torch.int64, device=ptr.device)
+    ws_n = _lib.lib().pg_schedule_count_dev_workspace(n_rows)
+    ws = _dev_ws(ws_n, ptr.device)
+    call("pg_schedule_count_dev", _lib.ptr(ptr), n_rows, chunk, _lib.ptr(counts), _lib.ptr(ws), ws.numel(),
+         _lib.stream_handle(ptr.device))
+    return counts
+
+
+def _schedule_build_dev(ptr: torch.Tensor, chunk: int, n_items: int, n_merges: int, max_deg: int):
+    """(items, merges) on ptr's device (pg_schedule_build_dev), sized as HostCsr's."""
+    n_rows = ptr.numel() - 1
+    items = torch.zeros(max(1, n_items) * 4, dtype=torch.int32, device=ptr.device)
+    merges = torch.zeros(max(1, n_merges) * 4, dtype=torch.int32, device=ptr.device)
+    ws_n = _lib.lib().pg_schedule_build_dev_workspace(n_rows, n_items, n_merges)
+    ws = _dev_ws(ws_n, ptr.device)
+    call("pg_schedule_build_dev", _lib.ptr(ptr), n_rows, chunk, n_items, n_merges, max_deg, _lib.ptr(items),
+         _lib.ptr(merges), _lib.ptr(ws), ws.numel(), _lib.stream_handle(ptr.device))
+    return items, merges
+
+
+def _transpose_dev(ptr: torch.Tensor, col: torch.Tensor, n_cols: int):
+    """(tptr, tcol, tslot, tpos, status) on ptr's device (pg_csr_transpose_dev)."""
+    dev = ptr.device
+    n_rows, nnz = ptr.numel() - 1, col.numel()
+    tptr = torch.empty(n_cols + 1, dtype=torch.int32, device=dev)
+    tcol, tslot, tpos = (torch.empty(nnz, dtype=torch.int32, device=dev) for _ in range(3))
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    ws_n = _lib.lib().pg_csr_transpose_dev_workspace(n_rows, n_cols, nnz)
+    ws = _dev_ws(ws_n, dev)
+    call("pg_csr_transpose_dev", _lib.ptr(ptr), _lib.ptr(col), n_rows, n_cols, nnz, _lib.ptr(tptr), _lib.ptr(tcol),
+         _lib.ptr(tslot), _lib.ptr(tpos), _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_handle(dev))
+    return tptr, tcol, tslot, tpos, status
+
 
 class DeviceGraph:
     def __init__(self, g: CSRGraph, device: torch.device):
@@ -247,9 +315,63 @@ class DeviceGraph:
         self.bwd = DeviceCsr(g.bwd, device)
         self.eid = torch.from_numpy(g.eid.astype(np.int64)).to(device)
 
+    @classmethod
+    def from_in_csr(cls, ptr: torch.Tensor, col: torch.Tensor, num_src: int, chunk: int = DEFAULT_CHUNK,
+                    chunk_bwd: Optional[int] = DEFAULT_CHUNK_BWD) -> "DeviceGraph":
+        """CSRGraph.from_in_csr(ptr, col, num_src).on(device) for an in-CSR that lives on a device
+        (int32 tensors): on a HIP device the transpose and both schedules are built there by
+        the device twins of the host calls, with one read-back (both directions' counts and the
+        status) and no copy of an index array; edge id = slot. ValueError for a column outside
+        [0, num_src) or a ptr that is not monotone from 0 to len(col)."""
+        if ptr.dtype != torch.int32 or col.dtype != torch.int32 or ptr.dim() != 1 or col.dim() != 1 \
+                or ptr.numel() < 1 or ptr.device != col.device:
+            raise TypeError("from_in_csr: ptr and col must be 1-D int32 tensors on one device")
+        dev, num_src = ptr.device, int(num_src)
+        if dev.type != "cuda":
+            return CSRGraph.from_in_csr(ptr.numpy(), col.numpy(), num_src, chunk, chunk_bwd).on("cpu")
+        ptr, col = ptr.contiguous(), col.contiguous()
+        num_dst, E = ptr.numel() - 1, col.numel()
+        if num_src < 0:
+            raise ValueError("from_in_csr: negative num_src")
+        if chunk_bwd is None:
+            chunk_bwd = default_chunk_bwd(max(num_src, num_dst))
+        cf = _schedule_count_dev(ptr, chunk)
+        tptr, tcol, tslot, tpos, status = _transpose_dev(ptr, col, num_src)
+        cb = _schedule_count_dev(tptr, chunk_bwd)
+        back = torch.cat([cf, cb, status.to(torch.int64)]).tolist()  # the one read-back
+        (fi, fm, fs, fmax, fmin, fst), (bi, bm, bs, bmax, _, bst), st = back[:6], back[6:12], back[12]
+        if st or fst or bst:
+            raise ValueError("from_in_csr: " + ("a column lies outside [0, num_src)" if st == -2 else
+                                                "ptr must start at 0, end at len(col) and be monotone"
+                                                if st or fst == -1 else "the schedule exceeds int32"))
+        fitems, fmerges = _schedule_build_dev(ptr, chunk, fi, fm, fmax)
+        bitems, bmerges = _schedule_build_dev(tptr, chunk_bwd, bi, bm, bmax)
+        g = cls.__new__(cls)
+        g.device = dev
+        g.num_src, g.num_dst, g.num_edges = num_src, num_dst, E
+        g.arg_kind = _lib.PG_ARG_U16 if fmax < 0xFFFF else _lib.PG_ARG_I32
+        g.arg_dtype = torch.int16 if g.arg_kind == _lib.PG_ARG_U16 else torch.int32
+        g.fwd = DeviceCsr.from_tensors(dev, ptr, col, None, None, fitems, fmerges, num_src, fi, fm, fs, fmax, chunk)
+        g.bwd = DeviceCsr.from_tensors(dev, tptr, tcol, tslot, tpos, bitems, bmerges, num_dst, bi, bm, bs, bmax,
+                                       chunk_bwd)
+        g.eid = torch.arange(E, dtype=torch.int64, device=dev)
+        g.min_in_degree = fmin
+        return g
+
     @property
     def num_nodes(self) -> int:
         return _square_nodes(self.num_src, self.num_dst)
+
+    def in_degrees(self) -> torch.Tensor:
+        """int32 in-degrees on the device (the differences of the in-CSR's ptr), computed once."""
+        if "_in_degrees" not in self.__dict__:
+            self._in_degrees = self.fwd.ptr.diff()
+        return self._in_degrees
+
+    def out_degrees(self) -> torch.Tensor:
+        if "_out_degrees" not in self.__dict__:
+            self._out_degrees = self.bwd.ptr.diff()
+        return self._out_degrees
 
     @property
     def is_cuda(self) -> bool:
@@ -278,3 +400,62 @@ class DeviceGraph:
         if w.numel() != self.num_edges:
             raise ValueError(f"edge_weight has {w.numel()} entries, graph has {self.num_edges} edges")
         return w.to(device=self.device, dtype=torch.float32).index_select(0, self.eid).contiguous()
+
+
+class DeviceBuiltGraph:
+    """Owner of a block whose engine graph was built on the device (DeviceGraph.from_in_csr): what
+    the dgl shim asks of a CSRGraph, answered without host arrays where it can be. `.on(its own
+    device)` is the device-built graph and `has_zero_in_degree()` comes from the count's minimum;
+    anything that needs host arrays (another device, in_degrees() / out_degrees() as numpy,
+    .fwd / .bwd / .eid) downloads ptr and col once and builds a CSRGraph.from_in_csr, kept in
+    `host` (None until then)."""
+
+    def __init__(self, ptr: torch.Tensor, col: torch.Tensor, num_src: int, chunk: int = DEFAULT_CHUNK,
+                 chunk_bwd: Optional[int] = DEFAULT_CHUNK_BWD):
+        self._chunk, self._chunk_bwd = chunk, chunk_bwd
+        self.device_graph = DeviceGraph.from_in_csr(ptr, col, num_src, chunk, chunk_bwd)
+        self.device = self.device_graph.device
+        self.num_src, self.num_dst = self.device_graph.num_src, self.device_graph.num_dst
+        self.num_edges = self.device_graph.num_edges
+        self.arg_kind = self.device_graph.arg_kind
+        self.host: Optional[CSRGraph] = None
+
+    def host_graph(self) -> CSRGraph:
+        if self.host is None:
+            f = self.device_graph.fwd
+            self.host = CSRGraph.from_in_csr(f.ptr.cpu().numpy(), f.col.cpu().numpy(), self.num_src, self._chunk,
+                                             self._chunk_bwd)
+        return self.host
+
+    @property
+    def num_nodes(self) -> int:
+        return _square_nodes(self.num_src, self.num_dst)
+
+    def on(self, device) -> DeviceGraph:
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device == self.device:
+            return self.device_graph
+        return self.host_graph().on(device)
+
+    def has_zero_in_degree(self) -> bool:
+        return self.num_dst > 0 and self.device_graph.min_in_degree == 0
+
+    def in_degrees(self) -> np.ndarray:
+        return self.host_graph().in_degrees()
+
+    def out_degrees(self) -> np.ndarray:
+        return self.host_graph().out_degrees()
+
+    @property
+    def fwd(self) -> HostCsr:
+        return self.host_graph().fwd
+
+    @property
+    def bwd(self) -> HostCsr:
+        return self.host_graph().bwd
+
+    @property
+    def eid(self) -> np.ndarray:
+        return self.host_graph().eid
