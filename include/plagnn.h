@@ -484,14 +484,20 @@ int pg_col_sum(const float* x, int64_t ldx, int64_t rows, int64_t cols, float* o
  *                                   + (1-t) log(clamp(1-p,1e-9,10))) / (w_c+1) * 2
  *   dz (if not NULL) = d loss / d z for rows in index, 0 elsewhere (all n_rows rows written).
  * class_w[2c] = (float)w_c and class_w[2c+1] = (float)(w_c + 1), both rounded from the
- * float64 weights of weight_cal (code/train.py:111-126). C <= 64. loss may be NULL. */
+ * float64 weights of weight_cal (code/train.py:111-126). C <= 64. loss may be NULL.
+ * n_index = 0 (index may then be NULL): prob and dz (all zeros) are still written for all
+ * n_rows rows; loss[0] is NOT written (there is no mean over no rows) and keeps its value. */
 /* The model head after liner1, fused (code/model.py:28-29, code/train.py:89-108, 199-207):
  *   z = A4 W2^T + b2;  prob = sigmoid(z);  multi_loss over the rows with row_set 1 (train,
  *   loss2[0], n = n_train) and row_set 2 (val, loss2[1], n = n_val);  dz = d loss2[0] / dz
  *   (0 outside the train rows);  dA4 = (dz W2) * leaky'(A4) with negative slope `slope`.
  * A4 [n][K] and dA4 [n][K] are f32 or bf16 (a_dtype); W2 [C][K], b2 [C] f32; K <= 128,
  * C <= 16. Optional outputs (NULL = skip): prob, dz, dz_bf16 (a bf16 copy of dz, leading
- * dimension lddz), dA4. Scratch: pg_mlp_head_workspace(n, C) bytes. */
+ * dimension lddz), dA4. Scratch: pg_mlp_head_workspace(n, C) bytes.
+ * n_train / n_val are the numbers of rows with row_set 1 / 2. An empty set's loss slot is
+ * NOT written and keeps its value (n_train = 0: loss2[0]; n_val = 0: loss2[1]); with
+ * n_train = 0, dz, dz_bf16 and dA4 are written as zeros for every row. prob does not depend
+ * on the sets. The same holds for pg_mlp_l1_head[_ex]. */
 size_t pg_mlp_head_workspace(int64_t n, int32_t C);
 int pg_mlp_head(const void* A4, int64_t lda, int64_t n, int32_t K, int a_dtype, const float* W2,
                 int64_t ldw, const float* b2, int32_t C, const float* labels, int64_t ldl,
