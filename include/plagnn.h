@@ -36,6 +36,10 @@
  *   pg_sample_fill,         dgl.to_block (include_dst_in_src): the per-batch work of a sampled mini-batch
  *   pg_block_compact        loop (dgl.dataloading.NeighborSampler). Not used by the reference, which trains
  *                           the full graph: reference-unpinned.
+ *   pg_sample_*_excl,    <- the same loop seeded by edges (dgl.dataloading.as_edge_prediction_sampler,
+ *   pg_edge_bits_update,    exclude_eids, dgl.dataloading.negative_sampler, g.has_edges_between /
+ *   pg_edge_lookup,         g.edge_ids)
+ *   pg_negative_sample
  *   pg_csr_transpose_dev,   <- the same loop: each sampled block's reverse CSR and both work schedules,
  *   pg_schedule_count_dev,     built where the block was sampled (the device twins of pg_csr_transpose /
  *   pg_schedule_build_dev      pg_schedule_*). Reference-unpinned.
@@ -427,6 +431,71 @@ int pg_block_compact(const int32_t* dst_ids, int64_t n_dst, const int32_t* col, 
                      int64_t n_parent, int32_t* src_ids, int32_t* col_local, int32_t* n_src_dev,
                      void* ws, size_t ws_bytes, pg_stream_t stream);
 
+/* ---------------- device: link-prediction mini-batches ---------------- */
+
+/* The per-batch work of an edge-seeded loop (dgl.dataloading.as_edge_prediction_sampler): sampling
+ * that leaves the seed edges out, edge lookup and negative pairs. Integer only; every entry point
+ * equals its _cpu twin bit for bit and follows the device contract above (enqueue on `stream`,
+ * scratch through (ws, ws_bytes), nothing allocated, copied to the host or synchronised, an
+ * argument error launches nothing, empty inputs succeed and read no buffer). Every id read from
+ * a caller's array is range-checked before it indexes anything. g is an in-CSR as for
+ * pg_sample_*; its schedule is not read.
+ *
+ * pg_edge_bits_update: a bit set over edge ids, bit (e & 31) of bits[e >> 5] for edge id e,
+ *   ceil(n_edge_ids / 32) words that the caller owns and zeroes once. set = 1 sets the bits of
+ *   eids[n] (atomic OR), set = 0 clears them (atomic AND): both order-independent, duplicates
+ *   are fine. An id outside [0, n_edge_ids) is skipped and stores -2 to *status_dev (int32,
+ *   device; written on that error only, so the caller zeroes it; NULL: not reported). A batch
+ *   sets its ids before sampling and clears the same ids afterwards: O(batch), not O(E).
+ * pg_sample_count_excl / pg_sample_fill_excl: pg_sample_count / pg_sample_fill on the graph
+ *   with the entries whose edge id has its bit set in excl_bits deleted and the edge ids kept:
+ *   row i holds min(deg - excluded in the row, fanout) entries, the ones with the fanout
+ *   smallest (sample key, edge id) among the entries that remain, in ascending edge id; a row
+ *   with at most fanout entries left (or fanout < 0) keeps them all in order. eid[nnz] maps
+ *   slots to edge ids (NULL: the identity); the count reads it too, the bit set being indexed
+ *   by edge id. excl_bits covers the edge ids [0, g->nnz) (an id outside counts as not
+ *   excluded) and must not change between the two calls; NULL gives pg_sample_*'s result bit
+ *   for bit. The count is one wave per seed row (it walks the row and tests the bits), then
+ *   the tile scan of pg_sample_count. The fill keeps pg_sample_fill's structure: one wave per
+ *   row, the bitwise threshold search over (key, position) composites counted with ballots. A
+ *   row of up to PG_SAMPLE_LDS_KEYS entries keeps its keys in LDS and its exclusion flags in
+ *   PG_SAMPLE_LDS_KEYS / 32 LDS words beside them, read from the bit set once; an excluded
+ *   entry's composite lies above every searched bit, so no pass counts it and the final
+ *   compare skips it. A longer row narrows to the surviving (key, position) pairs below a key
+ *   threshold estimated from the row's remaining count, as pg_sample_fill does from deg.
+ *   Workspace of the count: pg_sample_count_excl_workspace(n_seeds) bytes.
+ * pg_edge_lookup: out_eid[i] = the smallest edge id among the entries of row v[i] whose column
+ *   is u[i] (the edge u[i] -> v[i]; rows ascend in edge id, so the first matching position),
+ *   -1 when there is none or u[i] / v[i] lies outside the graph. One wave per pair scans the
+ *   row, the first match found with a ballot.
+ * pg_negative_sample: slot (i, j), j < k, writes index i * k + j. Attempts t = 0 .. tries - 1:
+ *   u = pos_src[i] (NULL: a draw over [0, g->n_cols)), v = a draw over [0, g->n_rows); the first
+ *   attempt that passes `flags` wins: PG_NEG_REJECT_EDGE rejects when u -> v is an edge (the
+ *   lookup above), PG_NEG_REJECT_SELF when u == v. A slot without a passing attempt, or with
+ *   pos_src[i] outside [0, g->n_cols), writes -1 to both outputs and counts in *n_fail_dev (int32,
+ *   device; zeroed by the call, then an integer atomic add). A draw is a 32-bit stateless
+ *   function of (seed64, pos_id[i] (NULL: i), j, t, which end) only (csrc/sample_key.hpp,
+ *   domain-separated from the neighbour sampler's key), mapped to a range of n by
+ *   ((uint64_t)key * n) >> 32: the result depends on the arguments only, never on the slot's
+ *   place in the batch, the launch shape or timing. 1 <= tries <= 64, k >= 1,
+ *   n_pos * k < 2^31. */
+#define PG_NEG_REJECT_EDGE 1
+#define PG_NEG_REJECT_SELF 2
+int pg_edge_bits_update(uint32_t* bits, int64_t n_edge_ids, const int32_t* eids, int64_t n, int set,
+                        int32_t* status_dev, pg_stream_t stream);
+size_t pg_sample_count_excl_workspace(int64_t n_seeds);
+int pg_sample_count_excl(const pg_csr_t* g, const int32_t* eid, const int32_t* seeds, int64_t n_seeds,
+                         int32_t fanout, const uint32_t* excl_bits, int32_t* out_ptr, void* ws,
+                         size_t ws_bytes, pg_stream_t stream);
+int pg_sample_fill_excl(const pg_csr_t* g, const int32_t* eid, const int32_t* seeds, int64_t n_seeds,
+                        int32_t fanout, uint64_t seed64, const uint32_t* excl_bits,
+                        const int32_t* out_ptr, int32_t* out_col, int32_t* out_eid, pg_stream_t stream);
+int pg_edge_lookup(const pg_csr_t* g, const int32_t* eid, const int32_t* u, const int32_t* v, int64_t n,
+                   int32_t* out_eid, pg_stream_t stream);
+int pg_negative_sample(const pg_csr_t* g, const int32_t* pos_src, const int32_t* pos_id, int64_t n_pos,
+                       int32_t k, int32_t tries, int flags, uint64_t seed64, int32_t* neg_src,
+                       int32_t* neg_dst, int32_t* n_fail_dev, pg_stream_t stream);
+
 /* A sampled block's transpose and schedules on the device: the twins of the host entry points
  * pg_csr_transpose / pg_schedule_count / pg_schedule_build on device pointers, equal to them bit
  * for bit (the host functions are the specification), so that dgl.dataloading.NeighborSampler
@@ -787,6 +856,22 @@ int pg_sample_fill_cpu(const pg_csr_t* g, const int32_t* eid, const int32_t* see
 int pg_block_compact_cpu(const int32_t* dst_ids, int64_t n_dst, const int32_t* col, int64_t nnz,
                          int64_t n_parent, int32_t* src_ids, int32_t* col_local, int32_t* n_src);
 
+/* The link-prediction primitives on host pointers: the statement of their results (the plain
+ * exact selection; the device entry points equal them bit for bit). No workspace; *status and
+ * *n_fail are host int32 (status written on an out-of-range id only, n_fail always). */
+int pg_edge_bits_update_cpu(uint32_t* bits, int64_t n_edge_ids, const int32_t* eids, int64_t n, int set,
+                            int32_t* status);
+int pg_sample_count_excl_cpu(const pg_csr_t* g, const int32_t* eid, const int32_t* seeds, int64_t n_seeds,
+                             int32_t fanout, const uint32_t* excl_bits, int32_t* out_ptr);
+int pg_sample_fill_excl_cpu(const pg_csr_t* g, const int32_t* eid, const int32_t* seeds, int64_t n_seeds,
+                            int32_t fanout, uint64_t seed64, const uint32_t* excl_bits,
+                            const int32_t* out_ptr, int32_t* out_col, int32_t* out_eid);
+int pg_edge_lookup_cpu(const pg_csr_t* g, const int32_t* eid, const int32_t* u, const int32_t* v, int64_t n,
+                       int32_t* out_eid);
+int pg_negative_sample_cpu(const pg_csr_t* g, const int32_t* pos_src, const int32_t* pos_id, int64_t n_pos,
+                           int32_t k, int32_t tries, int flags, uint64_t seed64, int32_t* neg_src,
+                           int32_t* neg_dst, int32_t* n_fail);
+
 /* ---------------- device: §8f — edge clustering coefficient ---------------- */
 
 /* code/data_preprocess.py:175-214 edge_clustering_coefficients on a symmetric adjacency
@@ -879,7 +964,11 @@ int pg_version(void); /* 2: pg_csr_t.einv; 3: pg_spmm_max_bwd fwd_out; 5: no in-
                          (neighbour sampling and block compaction);
                          13 also: pg_csr_transpose_dev, pg_schedule_count_dev,
                          pg_schedule_build_dev and their workspace queries (a sampled
-                         block's transpose and schedules on the device) */
+                         block's transpose and schedules on the device);
+                         13 also: pg_edge_bits_update, pg_sample_count_excl,
+                         pg_sample_count_excl_workspace, pg_sample_fill_excl, pg_edge_lookup,
+                         pg_negative_sample and the _cpu twins of the five (link-prediction
+                         mini-batches) */
 
 #ifdef __cplusplus
 }

@@ -612,4 +612,166 @@ int pg_block_compact_cpu(const int32_t* dst_ids, int64_t n_dst, const int32_t* c
   return pg::ok();
 }
 
+// ---- link-prediction mini-batches: the statement of the device results
+static inline bool edge_excluded(const uint32_t* bits, int64_t n_ids, int32_t e) {
+  return bits && e >= 0 && e < n_ids && ((bits[e >> 5] >> (e & 31)) & 1u);
+}
+
+int pg_edge_bits_update_cpu(uint32_t* bits, int64_t n_edge_ids, const int32_t* eids, int64_t n, int set,
+                            int32_t* status) {
+  const char* who = "pg_edge_bits_update_cpu";
+  if (n_edge_ids < 0 || n_edge_ids > INT32_MAX || n < 0 || n > INT32_MAX)
+    return pg::set_error(PG_ERR_INVALID, "%s: bad sizes", who);
+  if (n == 0) return pg::ok();
+  if (!eids || (n_edge_ids > 0 && !bits)) return pg::set_error(PG_ERR_INVALID, "%s: NULL buffer", who);
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t e = eids[i];
+    if (e < 0 || e >= n_edge_ids) {
+      if (status) *status = -2;
+      continue;
+    }
+    const uint32_t m = 1u << (e & 31);
+    if (set)
+      bits[e >> 5] |= m;
+    else
+      bits[e >> 5] &= ~m;
+  }
+  return pg::ok();
+}
+
+// the positions of row s (in range) whose edge id is not excluded
+static inline int32_t remaining_in_row(const pg_csr_t* g, const int32_t* eid, int32_t s, const uint32_t* bits) {
+  const int32_t b = g->ptr[s], deg = g->ptr[s + 1] - b;
+  int32_t rem = 0;
+  for (int32_t j = 0; j < deg; ++j) rem += !edge_excluded(bits, g->nnz, eid ? eid[b + j] : b + j);
+  return rem;
+}
+
+int pg_sample_count_excl_cpu(const pg_csr_t* g, const int32_t* eid, const int32_t* seeds, int64_t n_seeds,
+                             int32_t fanout, const uint32_t* excl_bits, int32_t* out_ptr) {
+  const char* who = "pg_sample_count_excl_cpu";
+  PG_TRY(pg::check_csr(g, who, false));
+  if (n_seeds < 0 || n_seeds > INT32_MAX || !out_ptr || (n_seeds > 0 && !seeds))
+    return pg::set_error(PG_ERR_INVALID, "%s: bad seeds / out_ptr", who);
+  int64_t run = 0;
+  for (int64_t i = 0; i < n_seeds; ++i) {
+    out_ptr[i] = (int32_t)run;
+    const int32_t s = seeds[i];
+    if (s < 0 || s >= g->n_rows) continue;
+    const int32_t rem = remaining_in_row(g, eid, s, excl_bits);
+    run += (fanout >= 0 && rem > fanout) ? fanout : rem;
+    if (run > INT32_MAX) return pg::set_error(PG_ERR_UNSUPPORTED, "%s: more than 2^31 sampled entries", who);
+  }
+  out_ptr[n_seeds] = (int32_t)run;
+  return pg::ok();
+}
+
+int pg_sample_fill_excl_cpu(const pg_csr_t* g, const int32_t* eid, const int32_t* seeds, int64_t n_seeds,
+                            int32_t fanout, uint64_t seed64, const uint32_t* excl_bits, const int32_t* out_ptr,
+                            int32_t* out_col, int32_t* out_eid) {
+  const char* who = "pg_sample_fill_excl_cpu";
+  PG_TRY(pg::check_csr(g, who, false));
+  if (n_seeds < 0 || n_seeds > INT32_MAX || !out_ptr || (n_seeds > 0 && !seeds))
+    return pg::set_error(PG_ERR_INVALID, "%s: bad seeds / out_ptr", who);
+  if (n_seeds == 0 || g->nnz == 0 || fanout == 0) return pg::ok();
+  if (!out_col || !out_eid) return pg::set_error(PG_ERR_INVALID, "%s: NULL output", who);
+  bool failed = false;
+#pragma omp parallel for schedule(dynamic, 64)
+  for (int64_t i = 0; i < n_seeds; ++i) {
+    const int32_t s = seeds[i];
+    if (s < 0 || s >= g->n_rows) continue;
+    const int32_t b = g->ptr[s], deg = g->ptr[s + 1] - b;
+    if (deg <= 0) continue;
+    const int64_t o = out_ptr[i];
+    // the (key, position) pairs that remain; positions ascend with the edge ids of a row
+    std::vector<std::pair<uint32_t, int32_t>> kp;
+    try {
+      kp.reserve((size_t)deg);
+    } catch (const std::bad_alloc&) {
+      failed = true;
+      continue;
+    }
+    for (int32_t j = 0; j < deg; ++j) {
+      const int32_t e = eid ? eid[b + j] : b + j;
+      if (!edge_excluded(excl_bits, g->nnz, e)) kp.push_back({pg::sample_key(seed64, e), j});
+    }
+    const int32_t rem = (int32_t)kp.size();
+    int32_t keep = rem;
+    if (fanout >= 0 && rem > fanout) {
+      std::nth_element(kp.begin(), kp.begin() + (fanout - 1), kp.end());
+      keep = fanout;
+    }
+    std::sort(kp.begin(), kp.begin() + keep,
+              [](const std::pair<uint32_t, int32_t>& x, const std::pair<uint32_t, int32_t>& y) {
+                return x.second < y.second;
+              });
+    for (int32_t q = 0; q < keep; ++q) {
+      const int32_t j = kp[(size_t)q].second;
+      out_col[o + q] = g->col[b + j];
+      out_eid[o + q] = eid ? eid[b + j] : b + j;
+    }
+  }
+  if (failed) return pg::set_error(PG_ERR_HOST, "%s: out of host memory", who);
+  return pg::ok();
+}
+
+// the slot of the first entry of row v (in range) whose column is u, -1: none
+static inline int32_t row_find(const pg_csr_t* g, int32_t v, int32_t u) {
+  for (int32_t k = g->ptr[v]; k < g->ptr[v + 1]; ++k)
+    if (g->col[k] == u) return k;
+  return -1;
+}
+
+int pg_edge_lookup_cpu(const pg_csr_t* g, const int32_t* eid, const int32_t* u, const int32_t* v, int64_t n,
+                       int32_t* out_eid) {
+  const char* who = "pg_edge_lookup_cpu";
+  PG_TRY(pg::check_csr(g, who, false));
+  if (n < 0 || n > INT32_MAX) return pg::set_error(PG_ERR_INVALID, "%s: bad n", who);
+  if (n == 0) return pg::ok();
+  if (!u || !v || !out_eid) return pg::set_error(PG_ERR_INVALID, "%s: NULL buffer", who);
+#pragma omp parallel for schedule(dynamic, 256)
+  for (int64_t i = 0; i < n; ++i) {
+    int32_t slot = -1;
+    if (u[i] >= 0 && u[i] < g->n_cols && v[i] >= 0 && v[i] < g->n_rows) slot = row_find(g, v[i], u[i]);
+    out_eid[i] = slot < 0 ? -1 : (eid ? eid[slot] : slot);
+  }
+  return pg::ok();
+}
+
+int pg_negative_sample_cpu(const pg_csr_t* g, const int32_t* pos_src, const int32_t* pos_id, int64_t n_pos,
+                           int32_t k, int32_t tries, int flags, uint64_t seed64, int32_t* neg_src,
+                           int32_t* neg_dst, int32_t* n_fail) {
+  const char* who = "pg_negative_sample_cpu";
+  PG_TRY(pg::check_csr(g, who, false));
+  if (n_pos < 0 || k < 1 || tries < 1 || tries > 64 || n_pos * (int64_t)k > INT32_MAX ||
+      (flags & ~(PG_NEG_REJECT_EDGE | PG_NEG_REJECT_SELF)))
+    return pg::set_error(PG_ERR_INVALID, "%s: n_pos >= 0, k >= 1, 1 <= tries <= 64, n_pos k < 2^31, known flags", who);
+  if (!n_fail || (n_pos > 0 && (!neg_src || !neg_dst))) return pg::set_error(PG_ERR_INVALID, "%s: NULL output", who);
+  int64_t fails = 0;
+  const int64_t n_slots = n_pos * k;
+#pragma omp parallel for schedule(dynamic, 256) reduction(+ : fails)
+  for (int64_t slot = 0; slot < n_slots; ++slot) {
+    const int64_t i = slot / k;
+    const int32_t j = (int32_t)(slot - i * k);
+    const int32_t id = pos_id ? pos_id[i] : (int32_t)i;
+    const int32_t fixed = pos_src ? pos_src[i] : 0;
+    int32_t ru = -1, rv = -1;
+    const bool can = g->n_rows > 0 && g->n_cols > 0 && fixed >= 0 && fixed < g->n_cols;
+    for (int32_t t = 0; can && t < tries; ++t) {
+      const int32_t uu = pos_src ? fixed : pg::key_to_range(pg::negative_key(seed64, id, j, t, 0), g->n_cols);
+      const int32_t vv = pg::key_to_range(pg::negative_key(seed64, id, j, t, 1), g->n_rows);
+      if ((flags & PG_NEG_REJECT_SELF) && uu == vv) continue;
+      if ((flags & PG_NEG_REJECT_EDGE) && row_find(g, vv, uu) >= 0) continue;
+      ru = uu;
+      rv = vv;
+      break;
+    }
+    neg_src[slot] = ru;
+    neg_dst[slot] = rv;
+    fails += ru < 0;
+  }
+  *n_fail = (int32_t)fails;
+  return pg::ok();
+}
+
 }  // extern "C"

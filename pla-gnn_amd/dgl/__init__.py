@@ -26,6 +26,11 @@ Mini-batch training (reference-unpinned): ``DGLBlock`` with separate ``srcdata``
 ``dgl.create_block``, ``dgl.to_block`` (pg_block_compact), ``dgl.sampling.sample_neighbors``
 (pg_sample_count, pg_sample_fill), ``dgl.dataloading``'s neighbour samplers and DataLoader, and
 blocks or (feat_src, feat_dst) pairs in the layers of ``dgl.nn.pytorch``.
+Link prediction (reference-unpinned): ``g.find_edges`` / ``has_edges_between`` / ``edge_ids``
+(pg_edge_lookup), ``exclude_edges`` / ``exclude_eids`` in the samplers (pg_edge_bits_update,
+pg_sample_count_excl, pg_sample_fill_excl), ``dgl.dataloading.negative_sampler`` and
+``dgl.sampling.global_uniform_negative_sampling`` (pg_negative_sample),
+``dgl.dataloading.as_edge_prediction_sampler`` and ``EdgeDataLoader``.
 
 Message passing on a CUDA (HIP) device always runs in libplagnn.so; a missing library is
 an error, never a silent fallback.
@@ -49,6 +54,10 @@ _SAMPLE_CALLS = 0
 _BINARY_OPS = ("add", "sub", "mul", "div")
 NID = "_ID"  # dgl.NID: parent node ids of a block's / subgraph's nodes
 EID = "_ID"  # dgl.EID: parent edge ids of its edges
+
+
+class DGLError(Exception):
+    """dgl.DGLError (dgl.base.DGLError): what DGL raises for a bad argument of a graph query."""
 
 
 def seed(val: int) -> None:
@@ -221,6 +230,47 @@ class DGLGraph:
 
     def is_homogeneous(self) -> bool:
         return True
+
+    # --- edge queries ----------------------------------------------------------------
+    def find_edges(self, eid, etype=None):
+        """(src, dst) of the edges with ids `eid`, on the graph's device."""
+        eid = _as_ids(eid).to(self._device)
+        if eid.numel() and (int(eid.min()) < 0 or int(eid.max()) >= self.num_edges()):
+            raise DGLError(f"find_edges: edge ids outside [0, {self.num_edges()})")
+        src, dst = self._uv(self._device)
+        return src[eid], dst[eid]
+
+    def _lookup(self, u, v) -> torch.Tensor:
+        """int32 edge id (the smallest) of every pair u[i] -> v[i], -1: no such edge
+        (pg_edge_lookup on the graph's device). Node ids must lie inside the graph."""
+        u, v = _as_ids(u).to(self._device), _as_ids(v).to(self._device)
+        if u.numel() != v.numel():
+            if u.numel() == 1:
+                u = u.expand(v.numel())
+            elif v.numel() == 1:
+                v = v.expand(u.numel())
+            else:
+                raise DGLError("the lengths of u and v differ")
+        for t, n in ((u, self.num_src_nodes()), (v, self.num_dst_nodes())):
+            if t.numel() and (int(t.min()) < 0 or int(t.max()) >= n):
+                raise DGLError(f"node ids outside [0, {n})")
+        return _engine().ops.edge_lookup(self._device_graph(self._device), u.contiguous(), v.contiguous())
+
+    def has_edges_between(self, u, v, etype=None) -> torch.Tensor:
+        """bool per pair: whether the graph holds an edge u[i] -> v[i]."""
+        return self._lookup(u, v) >= 0
+
+    def edge_ids(self, u, v, return_uv: bool = False, etype=None) -> torch.Tensor:
+        """The id of the edge u[i] -> v[i] per pair; where the graph holds it more than once, the
+        smallest id. A pair that is not an edge raises DGLError, as DGL does. return_uv=True
+        (every id of a multi-edge) is not supported."""
+        if return_uv:
+            raise NotImplementedError("edge_ids(return_uv=True) is not supported")
+        eid = self._lookup(u, v).to(torch.int64)
+        if eid.numel() and int(eid.min()) < 0:
+            i = int((eid < 0).nonzero()[0])
+            raise DGLError(f"edge_ids: no edge between the nodes of pair {i}")
+        return eid
 
     # --- placement -------------------------------------------------------------------
     def to(self, device, **kwargs) -> "DGLGraph":
@@ -654,5 +704,5 @@ def to_block(g: DGLGraph, dst_nodes=None, include_dst_in_src: bool = True) -> DG
 from . import sampling  # noqa: E402,F401  (dgl.sampling)
 from . import dataloading  # noqa: E402,F401  (dgl.dataloading)
 
-__all__ = ["DGLGraph", "DGLBlock", "graph", "create_block", "to_block", "add_self_loop", "remove_self_loop", "seed",
-           "NID", "EID", "function", "nn", "ops", "sampling", "dataloading"]
+__all__ = ["DGLGraph", "DGLBlock", "DGLError", "graph", "create_block", "to_block", "add_self_loop",
+           "remove_self_loop", "seed", "NID", "EID", "function", "nn", "ops", "sampling", "dataloading"]

@@ -84,6 +84,8 @@ class PgPad2d(ctypes.Structure):
 
 PG_PAD2D_MAX = 8
 PG_SAMPLE_LDS_KEYS = 2048  # rows up to this many entries keep their sampling keys in LDS
+PG_NEG_REJECT_EDGE = 1  # pg_negative_sample flags: no pair that is an edge, no u == v
+PG_NEG_REJECT_SELF = 2
 
 _i = ctypes.c_int
 _i32 = ctypes.c_int32
@@ -247,6 +249,17 @@ SIGNATURES = {
     "pg_sample_count_cpu": (_i, [_csr, _vp, _i64, _i32, _vp]),
     "pg_sample_fill_cpu": (_i, [_csr, _vp, _vp, _i64, _i32, ctypes.c_uint64, _vp, _vp, _vp]),
     "pg_block_compact_cpu": (_i, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "pg_edge_bits_update": (_i, [_vp, _i64, _vp, _i64, _i, _vp, _vp]),
+    "pg_sample_count_excl_workspace": (_sz, [_i64]),
+    "pg_sample_count_excl": (_i, [_csr, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "pg_sample_fill_excl": (_i, [_csr, _vp, _vp, _i64, _i32, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp]),
+    "pg_edge_lookup": (_i, [_csr, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "pg_negative_sample": (_i, [_csr, _vp, _vp, _i64, _i32, _i32, _i, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
+    "pg_edge_bits_update_cpu": (_i, [_vp, _i64, _vp, _i64, _i, _vp]),
+    "pg_sample_count_excl_cpu": (_i, [_csr, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "pg_sample_fill_excl_cpu": (_i, [_csr, _vp, _vp, _i64, _i32, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
+    "pg_edge_lookup_cpu": (_i, [_csr, _vp, _vp, _vp, _i64, _vp]),
+    "pg_negative_sample_cpu": (_i, [_csr, _vp, _vp, _i64, _i32, _i32, _i, ctypes.c_uint64, _vp, _vp, _vp]),
     "pg_last_error_string": (ctypes.c_char_p, []),
     "pg_version": (_i, []),
 }

@@ -387,6 +387,15 @@ class DeviceGraph:
             maps[transpose] = eid[self.bwd.eslot.long()].contiguous() if transpose else eid.contiguous()
         return maps[transpose]
 
+    def exclusion_bits(self) -> torch.Tensor:
+        """The graph's exclusion bit set (ops.sample_neighbors(exclude=)): int32 words on the device,
+        bit e & 31 of word e >> 5 for edge id e, allocated zeroed on first use. A batch sets its
+        ids (ops.edge_bits_update), samples, and clears the same ids: between batches it is zero."""
+        if "_exclusion_bits" not in self.__dict__:
+            self._exclusion_bits = torch.zeros(max(1, (self.num_edges + 31) // 32), dtype=torch.int32,
+                                               device=self.device)
+        return self._exclusion_bits
+
     def edge_weight_slots(self, edge_weight: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
         """Edge weights given per edge id (DGL order) -> in-CSR slot order, f32 contiguous:
         one weight per edge as a 1-D tensor, H > 1 weights per edge ((E, H, ...)) as (E, H)."""

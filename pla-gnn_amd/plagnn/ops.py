@@ -533,20 +533,56 @@ def _ids32(t, device, name: str) -> torch.Tensor:
     return t.to(device=device, dtype=torch.int32).contiguous()
 
 
-def sample_neighbors(dg: DeviceGraph, seeds, fanout: int, seed: int):
+def _excl_bits(dg: DeviceGraph, bits: torch.Tensor, name: str) -> torch.Tensor:
+    if bits.dtype != torch.int32 or bits.dim() != 1 or not bits.is_contiguous() or bits.device != dg.device \
+            or bits.numel() < (dg.num_edges + 31) // 32:
+        raise TypeError(f"{name}: the exclusion bit set is a contiguous int32 tensor of ceil(num_edges / 32) "
+                        "words on the graph's device (DeviceGraph.exclusion_bits())")
+    return bits
+
+
+def edge_bits_update(bits: torch.Tensor, n_edge_ids: int, eids, set: bool = True, check: bool = True) -> None:
+    """Set (or clear) the bits of edge ids `eids` in `bits` (pg_edge_bits_update): bit e & 31 of
+    word e >> 5 stands for edge id e; int32 words, in place, on bits' device. Duplicates are fine.
+    An id outside [0, n_edge_ids) is skipped; with `check` it raises ValueError after the update
+    (one device-to-host read of the status), without it nothing is read back."""
+    n_edge_ids = int(n_edge_ids)
+    if bits.dtype != torch.int32 or bits.dim() != 1 or not bits.is_contiguous() \
+            or bits.numel() < (n_edge_ids + 31) // 32:
+        raise TypeError("edge_bits_update: bits must be a contiguous int32 tensor of ceil(n_edge_ids / 32) words")
+    eids = _ids32(eids, bits.device, "edge_bits_update")
+    status = torch.zeros(1, dtype=torch.int32, device=bits.device) if check else None
+    args = (ptr(bits), n_edge_ids, ptr(eids), eids.numel(), 1 if set else 0, ptr(status))
+    if bits.device.type == "cuda":
+        call("pg_edge_bits_update", *args, _stream(bits))
+    else:
+        call("pg_edge_bits_update_cpu", *args)
+    if check and int(status[0]) != 0:
+        raise ValueError(f"edge_bits_update: edge ids outside [0, {n_edge_ids})")
+
+
+def sample_neighbors(dg: DeviceGraph, seeds, fanout: int, seed: int, exclude: Optional[torch.Tensor] = None):
     """Up to `fanout` in-edges of every seed node, without replacement (pg_sample_count +
     pg_sample_fill): (ptr, col, eid) of the sampled in-CSR, int32 on the graph's device, row i
     for seeds[i], col = parent source ids, eid = parent edge ids ascending in each row.
     fanout < 0 keeps whole rows. The result is a function of (graph, seeds, fanout, seed)
     only. One device-to-host read lies between the two calls: the entry count, and with it
     whether a seed lies outside the graph (ValueError; the count kernel itself takes such a seed
-    as a row without entries)."""
+    as a row without entries).
+
+    exclude: a bit set over the graph's edge ids (DeviceGraph.exclusion_bits(), filled by
+    edge_bits_update). The result is then that of the graph with those edges deleted and the
+    edge ids kept (pg_sample_count_excl + pg_sample_fill_excl): a row still receives `fanout`
+    neighbours from the edges that remain. None calls the plain entry points."""
     seeds = _ids32(seeds, dg.device, "sample_neighbors")
     n = seeds.numel()
     fanout, seed = int(fanout), int(seed) & 0xFFFFFFFFFFFFFFFF
     g = dg.fwd.struct(None)
     emap = dg.edge_map()
     out_ptr = torch.empty(n + 1, dtype=torch.int32, device=dg.device)
+    if exclude is not None:
+        return _sample_neighbors_excl(dg, g, emap, seeds, fanout, seed, _excl_bits(dg, exclude, "sample_neighbors"),
+                                      out_ptr)
     if dg.is_cuda:
         ws_n = _lib.lib().pg_sample_count_workspace(n)
         ws = _workspace(ws_n, dg.device)
@@ -566,6 +602,77 @@ def sample_neighbors(dg: DeviceGraph, seeds, fanout: int, seed: int):
         else:
             call("pg_sample_fill_cpu", *args)
     return out_ptr, col, eid
+
+
+def _sample_neighbors_excl(dg, g, emap, seeds, fanout, seed, bits, out_ptr):
+    n = seeds.numel()
+    if dg.is_cuda:
+        ws_n = _lib.lib().pg_sample_count_excl_workspace(n)
+        ws = _workspace(ws_n, dg.device)
+        call("pg_sample_count_excl", g, ptr(emap), ptr(seeds), n, fanout, ptr(bits), ptr(out_ptr), ptr(ws), ws_n,
+             _stream(out_ptr))
+    else:
+        call("pg_sample_count_excl_cpu", g, ptr(emap), ptr(seeds), n, fanout, ptr(bits), ptr(out_ptr))
+    bad = ((seeds < 0) | (seeds >= dg.num_dst)).any().to(torch.int32).reshape(1)
+    total, bad = torch.cat([out_ptr[n:], bad]).tolist()  # one read-back for both
+    if bad:
+        raise ValueError(f"sample_neighbors: seed ids outside [0, {dg.num_dst})")
+    col = torch.empty(total, dtype=torch.int32, device=dg.device)
+    eid = torch.empty(total, dtype=torch.int32, device=dg.device)
+    args = (g, ptr(emap), ptr(seeds), n, fanout, seed, ptr(bits), ptr(out_ptr), ptr(col), ptr(eid))
+    if total:
+        if dg.is_cuda:
+            call("pg_sample_fill_excl", *args, _stream(out_ptr))
+        else:
+            call("pg_sample_fill_excl_cpu", *args)
+    return out_ptr, col, eid
+
+
+def edge_lookup(dg: DeviceGraph, u, v) -> torch.Tensor:
+    """int32 edge id of every pair u[i] -> v[i] (pg_edge_lookup): the smallest id when the graph
+    holds the edge more than once, -1 when it does not hold it or an end lies outside the graph.
+    On the graph's device; nothing is read back."""
+    u = _ids32(u, dg.device, "edge_lookup")
+    v = _ids32(v, dg.device, "edge_lookup")
+    if u.numel() != v.numel():
+        raise ValueError("edge_lookup: u and v lengths differ")
+    out = torch.empty(u.numel(), dtype=torch.int32, device=dg.device)
+    args = (dg.fwd.struct(None), ptr(dg.edge_map()), ptr(u), ptr(v), u.numel(), ptr(out))
+    if dg.is_cuda:
+        call("pg_edge_lookup", *args, _stream(out))
+    else:
+        call("pg_edge_lookup_cpu", *args)
+    return out
+
+
+def negative_sample(dg: DeviceGraph, pos_src, pos_id, n_pos: int, k: int, seed: int, tries: int = 32,
+                    reject_edge: bool = False, reject_self: bool = False):
+    """k negative pairs per positive edge (pg_negative_sample): (neg_src, neg_dst, n_fail), int32
+    on the graph's device, slot (i, j) at i * k + j. The source is pos_src[i] (None: drawn over
+    the graph's sources), the destination is drawn over its destinations; up to `tries` attempts
+    per slot, the first that is no edge (reject_edge) and no self-pair (reject_self) wins. A slot
+    without one holds -1 in both outputs and counts in n_fail (a 1-element tensor: nothing is
+    read back here). The draws depend on (seed, pos_id[i] (None: i), j, attempt) only."""
+    n_pos, k = int(n_pos), int(k)
+    if pos_src is not None:
+        pos_src = _ids32(pos_src, dg.device, "negative_sample")
+    if pos_id is not None:
+        pos_id = _ids32(pos_id, dg.device, "negative_sample")
+    for t in (pos_src, pos_id):
+        if t is not None and t.numel() != n_pos:
+            raise ValueError("negative_sample: pos_src / pos_id must hold n_pos ids")
+    n_out = max(n_pos, 0) * max(k, 0)
+    neg_src = torch.empty(n_out, dtype=torch.int32, device=dg.device)
+    neg_dst = torch.empty(n_out, dtype=torch.int32, device=dg.device)
+    n_fail = torch.empty(1, dtype=torch.int32, device=dg.device)
+    flags = (_lib.PG_NEG_REJECT_EDGE if reject_edge else 0) | (_lib.PG_NEG_REJECT_SELF if reject_self else 0)
+    args = (dg.fwd.struct(None), ptr(pos_src), ptr(pos_id), n_pos, k, int(tries), flags,
+            int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(neg_src), ptr(neg_dst), ptr(n_fail))
+    if dg.is_cuda:
+        call("pg_negative_sample", *args, _stream(neg_src))
+    else:
+        call("pg_negative_sample_cpu", *args)
+    return neg_src, neg_dst, n_fail
 
 
 def block_compact(dst_ids, col, n_parent: int):

@@ -63,7 +63,7 @@ class Clock:
 
 
 def split_batch(g, seeds, build):
-    """One batch with the sampler's own steps (dgl/dataloading.py, plagnn/ops.py) and a
+    """One batch with the sampler's own steps (dgl/dataloading/__init__.py, plagnn/ops.py) and a
     synchronise after each part; returns the milliseconds per part."""
     from plagnn import _lib
     from plagnn._lib import call, ptr
