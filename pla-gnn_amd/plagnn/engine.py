@@ -25,7 +25,6 @@ stay exactly zero through forward, backward and Adam):
 from __future__ import annotations
 
 import contextlib
-import ctypes
 from collections import defaultdict
 from typing import Dict, List, Optional, Sequence
 
@@ -45,6 +44,11 @@ def launch_group(site: str) -> str:
     """Kernel group of a launch site name: every GEMM launch ('gemm.*') is 'gemm', the rest
     their prefix ('spmm_max_fwd.l1' -> 'spmm_max_fwd')."""
     return "gemm" if site.startswith("gemm") else site.split(".")[0]
+
+
+def pg_dtype(t: torch.Tensor) -> int:
+    """PG_DTYPE_* of a tensor's storage (f32 or bf16)."""
+    return _lib.PG_DTYPE_BF16 if t.dtype == torch.bfloat16 else _lib.PG_DTYPE_F32
 
 
 class _Flat:
@@ -76,10 +80,11 @@ class _Flat:
 
 
 class TrainEngine:
-    REDUCE_INLINE = False  # True: each split-K combine right after its partials (A/B knob)
-    # True: every weight gradient of the step in one grouped split-K launch at the end of the
-    # backward (pg_gemm_f32_group); False: one split-K launch per product (A/B knob)
-    GROUP_WGRAD = True
+    # ---- storage: what a subclass states to run the same step on other N-row tensors ----
+    ACT_DTYPE = torch.float32  # activations and activation gradients
+    WIDTH_ALIGN = 4            # every padded width is a multiple of this
+    GEMM = "pg_gemm_f32"       # the GEMM family: GEMM, GEMM_group, GEMM_group_workspace
+    SPMM_SUFFIX = ""           # pg_spmm_max_fwd / pg_spmm_max_bwd[_rows] + this
     # liner1's forward, the head and liner1's input gradient as one launch (pg_mlp_l1_head:
     # bitwise the separate x3 GEMMs + pg_mlp_head); False: three launches (A/B knob)
     FUSED_L1_HEAD = True
@@ -95,7 +100,6 @@ class TrainEngine:
     ACTIVE_TOP_ROWS = True
     _fold_prep = False             # set by the step paths (step_eager, capture, group_times)
     _prepped = False               # the head of this step formed the Adam scalars
-    WIDTH_ALIGN = 4  # every padded width is a multiple of this
     _cur = ""                      # launch site being issued (_t)
     _filter: Optional[str] = None  # group_times: issue only this launch group
     _issued = 0
@@ -125,12 +129,8 @@ class TrainEngine:
         dev = self.device
         a = self.WIDTH_ALIGN
         pd = [(d + a - 1) // a * a for d in self.dims]
-        # SAGE layer inputs: a multiple of 64 when that costs <= 2 % more columns (503 -> 512):
-        # whole feature tiles for the SpMM kernels; pads are zero and stay zero
-        for l in range(self.L):
-            r64 = -(-self.dims[l] // 64) * 64
-            if r64 <= 1.02 * self.dims[l]:
-                pd[l] = r64
+        for l in range(self.L):  # SAGE layer inputs: whole SpMM feature tiles when that is cheap
+            pd[l] = ops.sage_width(self.dims[l], a)
         self.pd = pd
 
         # ---- parameters (flat, padded) ----
@@ -160,12 +160,6 @@ class TrainEngine:
         self.adam_state = torch.zeros(4, dtype=torch.float32, device=dev)
         self.P = fl.views(self.flat)
         self.G = fl.views(self.gflat)
-        if params is None:
-            from .model import GNN
-
-            torch.manual_seed(seed)
-            params = GNN(self.dims).state_dict()
-        self.load_state_dict(params)
 
         # ---- inputs ----
         if tuple(features.shape) != (N, self.dims[0]):
@@ -196,14 +190,7 @@ class TrainEngine:
         self._setup_active_rows(rs == 1)
         self._alloc_buffers(features)
         self._alloc_workspace()
-        # W1's bf16 pieces for the fused head, kept current by the step's Adam
-        # (pg_adam_apply_l1) instead of split in every head call (pg_mlp_l1_split here and
-        # whenever the parameters are written from outside the step)
-        self.l1_pieces: Optional[torch.Tensor] = None
-        if self._l1_fused() and self.KEEP_L1_PIECES:
-            nb = int(_lib.lib().pg_mlp_l1_pieces_bytes(self.pd[-3], self.pd[-2]))
-            self.l1_pieces = torch.zeros(nb, dtype=torch.uint8, device=dev)
-            self._split_l1()
+        self._alloc_param_copies()
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.graph_adam: Optional[torch.cuda.CUDAGraph] = None
         self.allreduce = None
@@ -212,6 +199,23 @@ class TrainEngine:
         self.ar_events: Optional[list] = None
         self.steps_done = 0
         self._timing: Optional[list] = None  # [(name, work, start_event, end_event)]
+        # last: whatever the engine derives from the parameters has its buffers by now
+        if params is None:
+            from .model import GNN
+
+            torch.manual_seed(seed)
+            params = GNN(self.dims).state_dict()
+        self.load_state_dict(params)
+
+    def _alloc_param_copies(self) -> None:
+        """Buffers for what the engine derives from the parameters; params_updated() fills them.
+        W1's bf16 pieces for the fused head are kept current by the step's Adam
+        (pg_adam_apply_l1) instead of split in every head call, and split by pg_mlp_l1_split
+        whenever the parameters are written from outside the step."""
+        self.l1_pieces: Optional[torch.Tensor] = None
+        if self._l1_fused() and self.KEEP_L1_PIECES:
+            nb = int(_lib.lib().pg_mlp_l1_pieces_bytes(self.pd[-3], self.pd[-2]))
+            self.l1_pieces = torch.zeros(nb, dtype=torch.uint8, device=self.device)
 
     def _setup_active_rows(self, active: np.ndarray) -> None:
         """The train rows as the top layer's backward wants them (fixed for the engine's
@@ -244,7 +248,7 @@ class TrainEngine:
             return
         with self._t(tag, 2.0 * n * N * K):
             self._rows_gemm = _lib.call_supported(
-                "pg_gemm_f32_rows", 0, M, N, K, ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(C), C.stride(0),
+                self.GEMM + "_rows", 0, M, N, K, ptr(A), A.stride(0), ptr(B), B.stride(0), ptr(C), C.stride(0),
                 ptr(self.train_rows), n, self._s())
             self._issued += int(self._rows_gemm)
         if not self._rows_gemm:
@@ -266,26 +270,30 @@ class TrainEngine:
 
     def _alloc_buffers(self, features: torch.Tensor) -> None:
         N, pd, dev = self.N, self.pd, self.device
-        # ---- activations ----
+        # ---- activations (ACT_DTYPE); logits, losses and dZ are f32 in every storage ----
+        act = dict(dtype=self.ACT_DTYPE, device=dev)
         f32 = dict(dtype=torch.float32, device=dev)
         self.HM, self.Pl, self.arg = [], [], []
         for l in range(self.L):
             Fi = pd[l]
-            self.HM.append(torch.zeros(N, 2 * Fi, **f32))
-            self.Pl.append(torch.zeros(N, Fi, **f32))
+            self.HM.append(torch.zeros(N, 2 * Fi, **act))
+            self.Pl.append(torch.zeros(N, Fi, **act))
             self.arg.append(torch.zeros(N, Fi, dtype=self.dg.arg_dtype, device=dev))
-        self.HM[0][:, :self.dims[0]] = features.to(dev, torch.float32)
-        self.A3 = torch.zeros(N, pd[-3], **f32)
-        self.A4 = torch.zeros(N, pd[-2], **f32)
+        self.HM[0][:, :self.dims[0]] = features.to(dev, torch.float32).to(self.ACT_DTYPE)
+        self.A3 = torch.zeros(N, pd[-3], **act)
+        self.A4 = torch.zeros(N, pd[-2], **act)
         self.prob = torch.zeros(N, pd[-1], **f32)
         self.loss = torch.zeros(2, **f32)  # [train, val]
         # backward buffers: DYP_l = [dY_l | dP_l] (the gradients at layer l's pre-activation
         # output and at P_l, side by side: the stacked input-gradient product's A operand),
         # dM_l the gradient at the aggregated neighbourhood
         self.dZ = torch.zeros(N, pd[-1], **f32)
-        self.dA4 = torch.zeros(N, pd[-2], **f32)
-        self.DYP = [torch.zeros(N, pd[l + 1] + pd[l], **f32) for l in range(self.L)]
-        self.dM = [torch.zeros(N, pd[l], **f32) for l in range(self.L)]
+        # dZ in the activations' storage where that is not f32: the head writes it beside dZ,
+        # and liner2's weight gradient reads it
+        self.dZb = None if self.ACT_DTYPE == torch.float32 else torch.zeros(N, pd[-1], **act)
+        self.dA4 = torch.zeros(N, pd[-2], **act)
+        self.DYP = [torch.zeros(N, pd[l + 1] + pd[l], **act) for l in range(self.L)]
+        self.dM = [torch.zeros(N, pd[l], **act) for l in range(self.L)]
 
     def _alloc_workspace(self) -> None:
         # ---- workspace (one buffer, sized for the largest call) ----
@@ -296,21 +304,16 @@ class TrainEngine:
             Fi = pd[l]
             need = max(need, L.pg_spmm_max_fwd_workspace(self.dg.fwd.struct(self.ews), Fi, self.dg.arg_kind))
             need = max(need, L.pg_spmm_max_bwd_workspace(self.dg.bwd.struct(None), Fi))
-        self._gemm_plans = {}
-        # weight gradients' split-K combines deferred to one batched launch per step
-        self._slabs: Dict[str, torch.Tensor] = {}
-        self._jobs: list = []
+        # every weight gradient of the step waits in _parts (they only feed Adam) for one grouped
+        # split-K launch per gradient bucket (_reduce_deferred); the grouped launches' slabs are
+        # sized from the shapes alone (transposed A, plain B)
         self._parts: list = []
-        for (M_, N_, K_) in self._wgrad_shapes():
-            sk = ops._split_k(M_, N_, K_)
-            self._gemm_plans[(M_, N_, K_)] = sk
-            need = max(need, L.pg_gemm_f32_workspace(M_, N_, K_, sk))
-        if self.GROUP_WGRAD:
-            # the grouped launches' slabs, sized from the shapes alone (transposed A, plain B)
-            self.gws = torch.empty(self._group_ws_bytes(L.pg_gemm_f32_group_workspace), dtype=torch.uint8,
-                                   device=dev)
-        need = max(need, L.pg_sigmoid_multi_loss_workspace(N, C), L.pg_mlp_head_workspace(N, C),
-                   L.pg_mlp_l1_head_workspace(N, C, pd[-3], pd[-2]))
+        self.gws = torch.empty(self._group_ws_bytes(getattr(L, self.GEMM + "_group_workspace")),
+                               dtype=torch.uint8, device=dev)
+        # the head (fused with liner1 or not) and the standalone loss kernel
+        need = max(need, L.pg_sigmoid_multi_loss_workspace(N, C), L.pg_mlp_head_workspace(N, C))
+        if self._l1_fused():
+            need = max(need, L.pg_mlp_l1_head_workspace(N, C, pd[-3], pd[-2]))
         self.ws = torch.zeros(max(int(need), 256), dtype=torch.uint8, device=dev)
         self.ws_bytes = self.ws.numel()
 
@@ -381,8 +384,7 @@ class TrainEngine:
             self.P["liner1.b"][:d[-2]] = sd["liner1.bias"]
             self.P["liner2.W"][:d[-1], :d[-2]] = sd["liner2.weight"]
             self.P["liner2.b"][:d[-1]] = sd["liner2.bias"]
-        if getattr(self, "l1_pieces", None) is not None:
-            self._split_l1()
+        self.params_updated()
 
     def _split_l1(self) -> None:
         W1 = self.P["liner1.W"]
@@ -489,12 +491,7 @@ class TrainEngine:
             try:
                 with torch.cuda.graph(g, stream=s):
                     for _ in range(copies):
-                        self._fold_prep = True  # as the step runs it
-                        try:
-                            self.forward()
-                            self.backward()
-                        finally:
-                            self._fold_prep = False
+                        self._train_pass()
                         self.adam()
             finally:
                 self._filter = None
@@ -550,14 +547,11 @@ class TrainEngine:
         """Compulsory HBM bytes of the step's GEMM launches (each operand read once, each
         output written once, padded shapes), from a dry run that launches nothing."""
         self._rec, self._filter = [], "__dry_run__"
-        jobs = list(getattr(self, "_jobs", []))
         try:
             self.forward()
             self.backward()
         finally:
             out, self._rec, self._filter = sum(self._rec), None, None
-            if hasattr(self, "_jobs"):
-                self._jobs = jobs
         return int(out)
 
     def _gemm(self, A, B, C, transa=False, transb=False, beta=0.0, bias=None, act=NONE, dact=None,
@@ -569,87 +563,73 @@ class TrainEngine:
         # weight gradients (they feed only Adam) are recognised by their launch site, never by
         # shape: an input gradient of the same shape is read right after it is written
         wgrad = tag.startswith("gemm.wgrad")
-        if wgrad and (bias is not None or act != NONE or dact is not None):
-            raise ValueError(f"{tag}: a weight gradient takes no epilogue")
-        sk = self._gemm_plans.get((M, N, K), 1) if wgrad else 1
-        if self.GROUP_WGRAD and wgrad:
+        if wgrad:  # one part of the step's grouped launch (_reduce_deferred)
+            if C.dtype != torch.float32 or bias is not None or act != NONE or dact is not None:
+                raise ValueError(f"{tag}: a weight gradient has an f32 output and no epilogue")
             q = _lib.PgGemmPart()
             q.transa, q.transb, q.M, q.N, q.K = int(transa), int(transb), M, N, K
             q.A, q.lda, q.B, q.ldb = ptr(A), A.stride(0), ptr(B), B.stride(0)
             q.beta, q.C, q.ldc, q.rowsum = beta, ptr(C), C.stride(0), ptr(rowsum)
             self._parts.append((q, 2.0 * M * N * K))
             return
-        if sk > 1:
-            self._gemm_partials(A, B, C, transa, transb, beta, rowsum, tag, M, N, K, sk)
-            return
         ep = _lib.epilogue(bias, act, LEAKY_SLOPE, dact, rowsum)
-        ws = self.ws
         with self._t(tag, 2.0 * M * N * K):
-            self._call("pg_gemm_f32", int(transa), int(transb), M, N, K, 1.0, ptr(A), A.stride(0), ptr(B),
-                 B.stride(0), beta, ptr(C), C.stride(0), ep, sk, ptr(ws), ws.numel(), self._s())
+            self._gemm_launch(int(transa), int(transb), M, N, K, 1.0, ptr(A), A.stride(0), ptr(B), B.stride(0),
+                              beta, C, ep)
 
-    def _gemm_partials(self, A, B, C, transa, transb, beta, rowsum, tag, M, N, K, sk) -> None:
-        """A split-K weight gradient whose combine is deferred: the partial slabs go to this
-        launch site's own workspace and one pg_gemm_splitk_reduce_batch at the end of the
-        backward combines every weight gradient of the step (_reduce_deferred)."""
-        slab = self._slabs.get(tag)
-        if slab is None:
-            slab = torch.empty(int(_lib.lib().pg_gemm_f32_workspace(M, N, K, sk)), dtype=torch.uint8,
-                               device=self.device)
-            self._slabs[tag] = slab
-        used = ctypes.c_int(0)
-        ep = _lib.epilogue(rowsum=rowsum)
-        with self._t(tag, 2.0 * M * N * K):
-            self._call("pg_gemm_f32_partials", int(transa), int(transb), M, N, K, ptr(A), A.stride(0), ptr(B),
-                 B.stride(0), ep, sk, ptr(slab), slab.numel(), ctypes.byref(used), self._s())
-        j = _lib.PgSplitkJob()
-        j.ws, j.split_k, j.M, j.N = ptr(slab), used.value, M, N
-        j.alpha, j.beta, j.C, j.ldc, j.rowsum = 1.0, beta, ptr(C), C.stride(0), ptr(rowsum)
-        self._jobs.append(j)
-        if self.REDUCE_INLINE:  # combine now, while the slabs are still in the caches
-            self._reduce_deferred()
+    def _gemm_launch(self, transa, transb, M, N, K, alpha, A, lda, B, ldb, beta, C, ep) -> None:
+        """The GEMM family's plain entry, unsplit (C the output tensor, A and B pointers)."""
+        self._call(self.GEMM, transa, transb, M, N, K, alpha, A, lda, B, ldb, beta, ptr(C), C.stride(0), ep, 1,
+                   ptr(self.ws), self.ws_bytes, self._s())
 
     def _reduce_deferred(self) -> None:
+        """The pending weight gradients as one grouped split-K launch + one combine
+        (GEMM_group), chunked to the library's part limit per launch."""
         parts, self._parts = self._parts, []
-        for i in range(0, len(parts), MAX_GROUP_PARTS):  # the library's part limit per launch
+        for i in range(0, len(parts), MAX_GROUP_PARTS):
             chunk = parts[i:i + MAX_GROUP_PARTS]
             arr = (_lib.PgGemmPart * len(chunk))(*[q for q, _ in chunk])
             with self._t("gemm.wgrad.group", sum(w for _, w in chunk)):
-                self._call("pg_gemm_f32_group", arr, len(chunk), ptr(self.gws), self.gws.numel(), self._s())
-        jobs, self._jobs = self._jobs, []
-        for i in range(0, len(jobs), 16):
-            part = jobs[i:i + 16]
-            arr = (_lib.PgSplitkJob * len(part))(*part)
-            with self._t("gemm.splitk_reduce"):
-                self._call("pg_gemm_splitk_reduce_batch", arr, len(part), self._s())
+                self._call(self.GEMM + "_group", arr, len(chunk), ptr(self.gws), self.gws.numel(), self._s())
+
+    def _weights(self) -> Dict[str, torch.Tensor]:
+        """The weight operands of the step's products (Wpool, Wcat, liner1.W), in the
+        activations' storage. Biases and liner2 are read from the f32 parameters P always."""
+        return self.P
+
+    def _stack_weight(self, p: str):
+        """(B, transb) of layer p's stacked input-gradient product: [Wself ; Wpool]."""
+        return self.P[p + "Wstack"], False
 
     def forward(self) -> None:
         """Logits (self.prob) and both losses; dZ = d train_loss / d z."""
         st = self._s()
         g = self.dg.fwd.struct(self.ews)
-        P, pd = self.P, self.pd
+        P, W, pd = self.P, self._weights(), self.pd
         for l in range(self.L):
             p = f"conv{l + 1}."
             Fi = pd[l]
             HM = self.HM[l]
             # P = relu(H Wpool^T + bpool)
-            self._gemm(HM[:, :Fi], P[p + "Wpool"], self.Pl[l], transb=True, bias=P[p + "bpool"], act=RELU,
+            self._gemm(HM[:, :Fi], W[p + "Wpool"], self.Pl[l], transb=True, bias=P[p + "bpool"], act=RELU,
                        tag=f"gemm.fwd.pool.l{l + 1}")
             # M = max-aggregate(P) -> right half of HM
             with self._t(f"spmm_max_fwd.l{l + 1}", self.spmm_bytes(l)):
-                self._call("pg_spmm_max_fwd", g, ptr(self.Pl[l]), Fi, Fi, ptr(HM[:, Fi:]), HM.stride(0),
-                     ptr(self.arg[l]), Fi, self.dg.arg_kind | DEAD_NONE, ptr(self.ws), self.ws_bytes, st)
+                self._call("pg_spmm_max_fwd" + self.SPMM_SUFFIX, g, ptr(self.Pl[l]), Fi, Fi, ptr(HM[:, Fi:]),
+                           HM.stride(0), ptr(self.arg[l]), Fi, self.dg.arg_kind | DEAD_NONE, ptr(self.ws),
+                           self.ws_bytes, st)
             # Y = [H | M] Wcat^T + b (fc_self + fc_neigh + bias), leaky_relu -> next input
             Fo = pd[l + 1]
             out = self.HM[l + 1][:, :Fo] if l + 1 < self.L else self.A3
-            self._gemm(HM, P[p + "Wcat"], out, transb=True, bias=P[p + "b"], act=LEAKY,
+            self._gemm(HM, W[p + "Wcat"], out, transb=True, bias=P[p + "b"], act=LEAKY,
                        tag=f"gemm.fwd.cat.l{l + 1}")
         if self._l1_fused():
             self._mlp_l1_head()
             return
-        self._gemm(self.A3, P["liner1.W"], self.A4, transb=True, bias=P["liner1.b"], act=LEAKY,
+        self._gemm(self.A3, W["liner1.W"], self.A4, transb=True, bias=P["liner1.b"], act=LEAKY,
                    tag="gemm.fwd.liner1")
-        self._head(_lib.PG_DTYPE_F32, self.A4, self.dZ, None, self.dA4)
+        # liner2 + loss + dZ (+ its copy in the activations' storage) + dA4; f32 W2 / b2
+        self._head(pg_dtype(self.A4), self.A4, self.dZ, self.dZb, self.dA4)
 
     def _l1_fused(self) -> bool:
         return self.FUSED_L1_HEAD and self.pd[-2] <= 128
@@ -688,16 +668,17 @@ class TrainEngine:
 
     def backward(self) -> None:
         st = self._s()
-        G, P, pd = self.G, self.P, self.pd
+        G, W, pd = self.G, self._weights(), self.pd
         g = self.dg.fwd.struct(self.ews)
         gt = self.dg.bwd.struct(None)
         # liner2: dW2 = dZ^T A4 (+ db2 = row sums of dZ^T); dA4 came from the fused head
-        self._gemm(self.dZ, self.A4, G["liner2.W"], transa=True, rowsum=G["liner2.b"], tag="gemm.wgrad.liner2")
+        dZ = self.dZ if self.dZb is None else self.dZb
+        self._gemm(dZ, self.A4, G["liner2.W"], transa=True, rowsum=G["liner2.b"], tag="gemm.wgrad.liner2")
         # liner1
         self._gemm(self.dA4, self.A3, G["liner1.W"], transa=True, rowsum=G["liner1.b"], tag="gemm.wgrad.liner1")
         top = self.L - 1
         if not self._l1_fused():  # (fused: the head wrote the top layer's dY already)
-            self._gemm(self.dA4, P["liner1.W"], self.DYP[top][:, :pd[top + 1]], act=LEAKY, dact=self.A3,
+            self._gemm(self.dA4, W["liner1.W"], self.DYP[top][:, :pd[top + 1]], act=LEAKY, dact=self.A3,
                        tag="gemm.dgrad.liner1")
         for l in reversed(range(self.L)):
             p = f"conv{l + 1}."
@@ -706,17 +687,17 @@ class TrainEngine:
             dY, dP = DYP[:, :Fo], DYP[:, Fo:]
             # d Wcat = dY^T [H | M], d b = sum_nodes dY
             self._gemm(dY, HM, G[p + "Wcat"], transa=True, rowsum=G[p + "b"], tag=f"gemm.wgrad.cat.l{l + 1}")
-            # dM = dY Wneigh (top layer: the train rows only; dM's other rows are never read
-            # and stay the zeros they were allocated as)
-            if self._top_rows(l):
-                self._gemm_rows(dY, P[p + "Wcat"][:, Fi:], self.dM[l], tag=f"gemm.dgrad.neigh.l{l + 1}")
-            else:
-                self._gemm(dY, P[p + "Wcat"][:, Fi:], self.dM[l], tag=f"gemm.dgrad.neigh.l{l + 1}")
+            # dM = dY Wneigh, Wneigh = the right half of Wcat (top layer: the train rows only
+            # where the GEMM family has a row-list form; dM's other rows are never read and
+            # stay the zeros they were allocated as)
+            neigh = self._gemm_rows if self._top_rows(l) else self._gemm
+            neigh(dY, W[p + "Wcat"][:, Fi:], self.dM[l], tag=f"gemm.dgrad.neigh.l{l + 1}")
             # max backward; the records say "none" where M = 0 (DEAD_NONE), so those entries are
             # skipped and the relu' mask of fc_pool (P >= 0) is implied
             with self._t(f"spmm_max_bwd.l{l + 1}", self.spmm_bwd_bytes(l)):
-                self._max_bwd("pg_spmm_max_bwd", l, g, gt, ptr(self.arg[l]), Fi, self.dg.arg_kind | DEAD_NONE,
-                              ptr(self.dM[l]), Fi, Fi, ptr(self.Pl[l]), Fi, None, 0, ptr(dP), DYP.stride(0))
+                self._max_bwd("pg_spmm_max_bwd" + self.SPMM_SUFFIX, l, g, gt, ptr(self.arg[l]), Fi,
+                              self.dg.arg_kind | DEAD_NONE, ptr(self.dM[l]), Fi, Fi, ptr(self.Pl[l]), Fi, None, 0,
+                              ptr(dP), DYP.stride(0))
             # d Wpool = dP^T H, d bpool = sum_nodes dP
             self._gemm(dP, HM[:, :Fi], G[p + "Wpool"], transa=True, rowsum=G[p + "bpool"],
                        tag=f"gemm.wgrad.pool.l{l + 1}")
@@ -724,7 +705,8 @@ class TrainEngine:
             if l > 0:
                 # dH = ([dY | dP] [Wself ; Wpool]) * leaky'(H), one K = Fo + Fi product: the
                 # lower layer's dY (H is the previous layer's output)
-                self._gemm(DYP, P[p + "Wstack"], self.DYP[l - 1][:, :Fi], act=LEAKY, dact=HM[:, :Fi],
+                B, transb = self._stack_weight(p)
+                self._gemm(DYP, B, self.DYP[l - 1][:, :Fi], transb=transb, act=LEAKY, dact=HM[:, :Fi],
                            tag=f"gemm.dgrad.stack.l{l + 1}")
         self._reduce_deferred()
         self._bucket_done(len(self.grad_buckets()) - 1)
@@ -742,16 +724,11 @@ class TrainEngine:
         """Bucket i's all-reduce may start only once every gradient inside its range has been
         issued: each parameter block in the range must be the output (or row-sum output) of a
         weight-gradient launch still pending in this flush (a Wcp block is written as its Wcat
-        rows and its Wpool rows; its zero pad is never written). Ungrouped weight gradients
-        (the GROUP_WGRAD = False A/B knob) were launched in stream order already."""
-        if not self.GROUP_WGRAD:
-            return
+        rows and its Wpool rows; its zero pad is never written)."""
         a, b = self.grad_buckets()[i]
         pending = set()
         for q, _ in self._parts:
             pending.update((q.C or 0, q.rowsum or 0))
-        for j in getattr(self, "_jobs", []):
-            pending.update((j.C or 0, j.rowsum or 0))
         need = []
         for name, off in self.flat_layout.offsets.items():
             if a <= off < b:
@@ -792,17 +769,21 @@ class TrainEngine:
                 raise ValueError(f"all-reduce buckets {got} are not this engine's grad_buckets() {want}")
         self._split_buckets = bk is not None and len(bk) > 1
 
-    def step_eager(self, allreduce=None) -> None:
-        self._uses_buckets(allreduce)
-        inline = allreduce is not None and getattr(allreduce, "capturable", False)
-        self._ar_inline = allreduce if inline else None
-        self._fold_prep = True
+    def _train_pass(self, ar_inline=None) -> None:
+        """forward + backward as a training step issues them (a bare forward() is not one):
+        the head may form the step's Adam scalars (_fold_prep), and with `ar_inline` the
+        backward starts each gradient bucket's all-reduce as the bucket completes."""
+        self._ar_inline, self._fold_prep = ar_inline, True
         try:
             self.forward()
             self.backward()
         finally:
-            self._ar_inline = None
-            self._fold_prep = False
+            self._ar_inline, self._fold_prep = None, False
+
+    def step_eager(self, allreduce=None) -> None:
+        self._uses_buckets(allreduce)
+        inline = allreduce is not None and getattr(allreduce, "capturable", False)
+        self._train_pass(allreduce if inline else None)
         if inline:
             allreduce.join()
         elif allreduce is not None:
@@ -831,25 +812,13 @@ class TrainEngine:
         self.graph_adam = None
         if allreduce is None or inline:
             with torch.cuda.graph(self.graph):
-                self._ar_inline = allreduce if inline else None
-                self._fold_prep = True
-                try:
-                    self.forward()
-                    self.backward()
-                finally:
-                    self._ar_inline = None
-                    self._fold_prep = False
+                self._train_pass(allreduce if inline else None)
                 if inline:
                     allreduce.join()
                 self.adam()
         else:
             with torch.cuda.graph(self.graph):
-                self._fold_prep = True
-                try:
-                    self.forward()
-                    self.backward()
-                finally:
-                    self._fold_prep = False
+                self._train_pass()
             self.graph_adam = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph_adam):
                 self.adam()
@@ -890,11 +859,11 @@ class TrainEngine:
 
     def spmm_bytes(self, layer: int) -> int:
         """Algorithmic HBM bytes of one max-aggregation forward:
-        4(N+1) + 4E' + s*F*E' + s*F*N + a*F*N, s = 4 (f32), a = argpos bytes, at the true
-        (unpadded) width F."""
-        N, E, F = self.N, self.dg.num_edges, self.dims[layer]
+        4(N+1) + 4E' + s*F*E' + s*F*N + a*F*N, s = the activations' element size (4 for f32,
+        2 for bf16), a = argpos bytes, at the true (unpadded) width F."""
+        N, E, F, s = self.N, self.dg.num_edges, self.dims[layer], self.ACT_DTYPE.itemsize
         a = 2 if self.dg.arg_kind == _lib.PG_ARG_U16 else 4
-        return 4 * (N + 1) + 4 * E + 4 * F * E + 4 * F * N + a * F * N
+        return 4 * (N + 1) + 4 * E + s * F * E + s * F * N + a * F * N
 
     def spmm_bwd_bytes(self, layer: int) -> int:
         """Algorithmic bytes of one max backward: the upstream gradient
@@ -902,10 +871,10 @@ class TrainEngine:
         top layer's active-rows form), dX written once (s*F*N), plus the transposed CSR
         (4(N+1) + 8E'), true width F. No relu-mask read: the dead-none records imply the
         mask and the kernel never loads it."""
-        N, E, F = self.N, self.dg.num_edges, self.dims[layer]
+        N, E, F, s = self.N, self.dg.num_edges, self.dims[layer], self.ACT_DTYPE.itemsize
         a = 2 if self.dg.arg_kind == _lib.PG_ARG_U16 else 4
         Na = self.train_rows.numel() if self._top_rows(layer) and self._rows_spmm else N
-        return 4 * (N + 1) + 8 * E + 4 * F * N + (4 + a) * F * Na
+        return 4 * (N + 1) + 8 * E + s * F * N + (s + a) * F * Na
 
     def flops_per_step(self) -> int:
         """Flops of the step's GEMM launches at the true (unpadded) dims, forward + backward

@@ -1219,12 +1219,12 @@ def _padded(n: int, F: int, device) -> torch.Tensor:
     return buf
 
 
-def sage_width(F: int) -> int:
+def sage_width(F: int, align: int = 4) -> int:
     """TrainEngine's SAGE input width: a multiple of 64 when that costs <= 2 % more columns
     (503 -> 512: whole SpMM feature tiles, the three-piece GEMM's aligned operands), else a
-    multiple of 4. Pads are zero."""
+    multiple of `align` (the engine's WIDTH_ALIGN). Pads are zero and stay zero."""
     r64 = -(-F // 64) * 64
-    return r64 if r64 <= 1.02 * F else round4(F)
+    return r64 if r64 <= 1.02 * F else -(-F // align) * align
 
 
 # layer inputs that take no gradient (the features: the same tensor every epoch) keep their

@@ -21,15 +21,6 @@ def main():
     cfg = os.environ.get("CONFIG", "cfg2")
     wl = W.build(cfg, device="cuda")
     Engine = plagnn.TrainEngineBF16 if wl.bf16 else plagnn.TrainEngine
-    if os.environ.get("PG_REDUCE_INLINE") is not None:  # A/B of the split-K combine placement
-        plagnn.TrainEngine.REDUCE_INLINE = os.environ["PG_REDUCE_INLINE"] == "1"
-        label += f"+inline{os.environ['PG_REDUCE_INLINE']}"
-    if os.environ.get("PG_GROUP_WGRAD") is not None:  # A/B of the grouped weight gradients
-        plagnn.TrainEngine.GROUP_WGRAD = os.environ["PG_GROUP_WGRAD"] == "1"
-        label += f"+group{os.environ['PG_GROUP_WGRAD']}"
-    if wl.bf16 and os.environ.get("PG_STACK_T") is not None:  # A/B of the stacked-weight layout
-        plagnn.TrainEngineBF16.STACK_T = os.environ["PG_STACK_T"] == "1"
-        label += f"+stackT{os.environ['PG_STACK_T']}"
     e = Engine(wl.graph(), torch.from_numpy(wl.ds.feat), torch.from_numpy(wl.ds.loc.astype(np.float32)),
                wl.dims, wl.class_weight, wl.train_index, wl.val_index, lr=5e-5, device="cuda",
                edge_weight=wl.edge_weight)
