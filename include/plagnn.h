@@ -879,8 +879,11 @@ int pg_negative_sample_cpu(const pg_csr_t* g, const int32_t* pos_src, const int3
  *   ecc[k] for entry k = (i, j), i != j:
  *     epsilon if min(deg_i, deg_j) - 1 == 0, else |N(i) ∩ N(j)| / (min(deg_i, deg_j) - 1)
  *   deg = row sums of the stored values (NULL: row lengths); diagonal entries get 0.
- * mirror[k] = index of the entry (j, i); order = rows longest first (optional, speed only).
- * n <= 2^22 (the neighbour bitmap of a row lives in LDS). Bit-exact (integer counts, one
+ * mirror[k] = index of the entry (j, i); order = any permutation of the rows, or NULL for
+ * 0..n-1 (speed only: longest first balances the workgroups; the result does not depend on it).
+ * n <= 1 310 720: the neighbour bitmap of a row lives in LDS, one bit per node in at most
+ * 160 KB (above 64 KB fewer workgroups share a CU). Larger n: PG_ERR_UNSUPPORTED up to 2^22,
+ * PG_ERR_INVALID beyond. n == 0 or nnz == 0 writes nothing. Bit-exact (integer counts, one
  * f64 division). */
 int pg_ecc(const int32_t* ptr, const int32_t* col, const int32_t* mirror, const double* deg,
            const int32_t* order, int64_t n, int64_t nnz, double epsilon, double* ecc,

@@ -98,6 +98,28 @@ def gen_ecc():
     np.savez(os.path.join(HERE, "ecc.npz"), **out)
 
 
+def gen_ecc_weighted():
+    """edge_clustering_coefficients with epsilon = 0.25 on tests/preproc_common.py's weighted
+    graph (72 nodes, symmetric weights in {1, 2, 3}, diagonal entries on about 30 % of the
+    nodes: the degree is the row sum, not the row length) and on the same graph with the
+    weights halved (min(deg) - 1 takes fractional, zero and negative values). Stored: the
+    input COO and the function's output COO, in the order it emits them."""
+    sys.path.insert(0, REF)
+    sys.path.insert(0, os.path.dirname(HERE))
+    import data_preprocess as dp  # noqa: E402
+    from preproc_common import weighted_graph
+    from scipy.sparse import coo_matrix
+
+    r, c, w, n = weighted_graph()
+    out = {"n": np.int64(n), "row": r, "col": c, "epsilon": np.float64(0.25)}
+    for name, scale in (("w", 1.0), ("half", 0.5)):
+        e = dp.edge_clustering_coefficients(coo_matrix((w * scale, (r, c)), shape=(n, n)), epsilon=0.25).tocoo()
+        out[f"{name}_val"] = w * scale
+        out[f"{name}_ecc_row"], out[f"{name}_ecc_col"] = e.row.astype(np.int64), e.col.astype(np.int64)
+        out[f"{name}_ecc_val"] = np.asarray(e.data, np.float64)
+    np.savez_compressed(os.path.join(HERE, "ecc_weighted.npz"), **out)
+
+
 def gen_perturb():
     """Reference end to end: a GEO-style expression CSV (duplicate ids averaged, ids not in
     the PPI dropped, PPI proteins missing from the CSV zero-filled) -> construct_gcn_matrix
@@ -184,6 +206,8 @@ if __name__ == "__main__":
         gen_eval(ns)
     if not only or "ecc" in only:
         gen_ecc()
+    if not only or "ecc_weighted" in only:  # a fixture file of its own
+        gen_ecc_weighted()
     if not only or "perturb" in only:
         gen_perturb()
     if not only or "pca" in only:
