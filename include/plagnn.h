@@ -181,6 +181,41 @@ int pg_schedule_build(const int32_t* ptr, int64_t n_rows, int32_t chunk, int32_t
 
 /* ---------------- device: message passing ---------------- */
 
+/* Leading dimensions and alignment of the max family (pg_spmm_max_fwd, pg_spmm_max_bwd,
+ * pg_spmm_max_bwd_rows, their _bf16 forms, pg_spmm_max_bwd_scatter, pg_argpos_to_src). E is the
+ * feature element (4 bytes, 2 for the _bf16 forms), R the record (2 bytes for PG_ARG_U16, 4 for
+ * PG_ARG_I32). Every 2-D operand is row-major with its own leading dimension >= F (else
+ * PG_ERR_INVALID, nothing launched) and a base pointer aligned to its element. For every entry
+ * point: nothing outside the F columns of a row is written (pad columns of out, argpos, dx and
+ * argx, and everything before and after the rows, keep their bytes), no value outside the F
+ * columns of an input's rows influences a result, and every element inside the F columns of an
+ * output is written by every call (no zero fill by the caller, rows without entries included).
+ * The result does not depend on the path taken: the paths below differ in access width only.
+ *   pg_spmm_max_fwd[_bf16]: the vector path (16-byte accesses of X, out and the workspace
+ *     values, 4 R-byte accesses of the records) needs F, ldx, ldo and lda multiples of 4, X,
+ *     out and ws 16-byte aligned and argpos aligned to 4 R (8 bytes for u16 records, 16 for
+ *     i32). Anything else takes the scalar path (element accesses, 1024 columns per feature
+ *     tile, split rows combined by a second launch). On the vector path split rows are
+ *     combined inside the launch when ws is also 256-byte aligned, else by a second launch.
+ *     ws: 4-byte aligned at least.
+ *   pg_spmm_max_bwd[_rows][_bf16], grouped form (PG_ARG_U16 records, F <= 1024, N F < 2^31),
+ *     two independent decisions. Pack: vector when F, lda, ldd (and ldf with fwd_out) are
+ *     multiples of 4, argpos is 8-byte aligned and dout (and fwd_out) aligned to 4 E; else
+ *     element accesses of all three. Pull: a split source row is combined inside the pull's
+ *     launch when F and ldx are multiples of 4 and dx is aligned to 4 E, and, where the mask is
+ *     read (mask_src given and no PG_ARG_DEAD_NONE), ldm is a multiple of 4 and mask_src
+ *     aligned to 4 E; else by a second launch (element accesses of dx and mask_src unless its
+ *     own rows are 4-aligned). With PG_ARG_DEAD_NONE mask_src is not read at all. _rows: the
+ *     same; row_active and eslot_active are flat arrays.
+ *   pg_spmm_max_bwd, record gather (PG_ARG_I32 records or F > 1024; f32 only): the vector path
+ *     needs F, lda, ldd, ldx (and ldm with a mask) multiples of 4, dout, dx, mask_src and ws
+ *     16-byte aligned and argpos aligned to 4 R; else the scalar path, 1024 columns per launch.
+ *   ws of pg_spmm_max_bwd[_rows][_bf16] must be 16-byte aligned (PG_ERR_INVALID otherwise,
+ *     nothing launched): its regions (partial rows | records | descriptors | tickets) start
+ *     multiples of 256 bytes past ws and are accessed 16 bytes at a time.
+ *   pg_spmm_max_bwd_scatter, pg_argpos_to_src: element accesses only, no alignment beyond the
+ *     element's; lda, ldd, ldx are free (>= F). */
+
 /* out[v,f] = max_{k in row v} (ew? ew[k]:1) * X[col[k], f]  (strict >, first wins, start -inf);
  * argpos[v,f] = k - ptr[v] of the winner. Rows with no entries: out = 0, argpos = none.
  * A +-inf result is stored as 0 (DGL's replace_inf_with_zero after a max reduce).

@@ -862,6 +862,10 @@ int max_bwd_entry(const pg_csr_t* g, const pg_csr_t* gt, const void* argpos, int
     return pg::set_error(PG_ERR_INVALID, "pg_spmm_max_bwd_rows: row_active and eslot_active go together");
   const size_t need = pg_spmm_max_bwd_workspace(gt, F);
   PG_TRY(check_ws(ws_bytes, need, "pg_spmm_max_bwd"));
+  // every region below starts a multiple of 256 B past ws: the records (uint2, 16-B copies),
+  // the descriptors' uint4 clear and the partial rows' 16-B slot accesses inherit ws's alignment
+  if (need > 0 && !aligned16(ws))
+    return pg::set_error(PG_ERR_INVALID, "pg_spmm_max_bwd: ws must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
   const size_t pbytes = bwd_partials_bytes(gt, F);
   float* w = pbytes ? (float*)ws : nullptr;

@@ -31,63 +31,14 @@ Branches (F is the smallest width that reaches each; f32 widths, bf16 where it d
   backward on active rows (pg_spmm_max_bwd_rows) with a hub row inactive.
 No case is left to test_gpu_kernels.py: the shapes here are small enough to run them all.
 """
-import functools
-
 import numpy as np
 import pytest
 import torch
 
-import sum_common as sm
+from max_common import case as _case, graph as _graph, same as _same
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-CHUNK = 4
-
-
-@functools.lru_cache(maxsize=None)
-def _graph(trans=False, i32=False):
-    """The ladder graph at chunk 4 (sum_common.ladder_graph checks its degrees); trans: with
-    the in-CSR slots' transposed indices (g->epos); i32: 4-byte records on a graph whose
-    degrees would fit u16."""
-    import plagnn
-    from plagnn import _lib
-
-    base = sm.ladder_graph(chunk=CHUNK)
-    if not trans and not i32:
-        g = base
-    else:
-        src, dst, degs = sm.ladder_coo(CHUNK)
-        g = plagnn.CSRGraph(src, dst, len(degs), chunk=CHUNK, bwd_trans=trans)
-        if i32:
-            g.arg_kind = _lib.PG_ARG_I32
-    assert g.bwd_trans == trans and (g.fwd.epos is not None) == trans
-    assert g.fwd.n_merges >= 3 and g.bwd.n_merges > 0 and g.bwd.epos is not None
-    return g
-
-
-@functools.lru_cache(maxsize=None)
-def _case(F, weighted, i32):
-    """(X, w, out, argpos, dout, dx, dx_masked) of one shape from the host twins, computed once
-    and never modified; w in in-CSR slot order or None."""
-    from plagnn import ops
-
-    g = _graph(False, i32)
-    rng = np.random.default_rng(7 * F + weighted)
-    X = rng.integers(-3, 4, (g.num_src, F)).astype(np.float32)
-    X[rng.random(X.shape) < 0.3] = 0.0
-    w = rng.choice(np.array([-1.0, 0.5, 1.0, 2.0], np.float32), g.num_edges) if weighted else None
-    dout = rng.integers(-4, 5, (g.num_dst, F)).astype(np.float32)
-    cg = g.on("cpu")
-    Xt, dt = torch.from_numpy(X), torch.from_numpy(dout)
-    wt = None if w is None else torch.from_numpy(w)
-    out, arg = ops.spmm_max(cg, Xt, wt)
-    dx = ops.spmm_max_backward(cg, arg, dt, wt)
-    dxm = ops.spmm_max_backward(cg, arg, dt, wt, mask=Xt)
-    res = tuple(None if t is None else t.numpy() for t in (Xt, wt, out, arg, dt, dx, dxm))
-    for a in res:
-        if a is not None:
-            a.setflags(write=False)
-    return res
 
 
 def _dev(a, dtype=torch.float32, offset=False):
@@ -105,15 +56,6 @@ def _dev(a, dtype=torch.float32, offset=False):
         assert v.data_ptr() % 16 == t.element_size()
         t = v
     return t
-
-
-def _same(got, want, name):
-    """got (f32 or bf16, on the device) holds exactly the f32 twin's bits; bf16 storage: the
-    twin's values rounded once to bf16 (round to nearest even, as the kernels' stores)."""
-    assert tuple(got.shape) == want.shape, name
-    if got.dtype == torch.bfloat16:
-        want = torch.from_numpy(np.array(want)).to(torch.bfloat16).float().numpy()
-    sm.assert_bits(got.float(), want, name)
 
 
 def _offset_workspace(monkeypatch, off=16):
